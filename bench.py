@@ -8,9 +8,11 @@ synthetic voxels already resident in HBM.  Workload at N=1: BASELINE.json config
 (one process per GPU, torchrun) every rank owns its own 1 M-voxel shard (weak scaling) and the three
 masked sums are all-reduced over RCCL every step.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (dominant kernel vi_fwd_kernel, timed
-with HIP events on the launch stream) and "cpu_baseline" (the oracle's literal-Simpson restatement
-on the host cores, bounded sample).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps, writes the last step's
+outputs if --dump-outputs is given, and prints the headline.  --full adds: "roofline" (dominant kernel
+vi_fwd_kernel, timed with HIP events on the launch stream), "variants" and "training_step" (the other
+workloads the summaries quote) and "cpu_baseline" (the oracle's literal-Simpson restatement on the host
+cores, bounded sample).
 """
 import argparse
 import configparser
@@ -179,6 +181,32 @@ def cpu_baseline(params, weights_np, S, K, budget_s=15.0):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays the timed path returned in its last step, one DIR/<name>.npy each (sums float64,
+    the per-voxel arrays float32).  When the per-voxel arrays exceed `limit` bytes in all, the same fixed, seeded
+    sample of voxels (sorted rows, generator seed 0) is taken from each of them."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rows = {k: v for k, v in outputs.items() if v is not None and v.dim() == 2}
+    n = next(iter(rows.values())).shape[0] if rows else 0
+    row_bytes = sum(v.shape[1] * v.element_size() for v in rows.values())
+    idx = None
+    if n * row_bytes > limit - 4096:
+        m = (limit - 4096) // row_bytes
+        idx = np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+        idx = torch.as_tensor(idx, device=next(iter(rows.values())).device)
+    for name, t in outputs.items():
+        if t is None:
+            continue
+        if idx is not None and name in rows:
+            t = t.index_select(0, idx)
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -301,10 +329,11 @@ class Spec:
         self.wide_posterior, self.off_grid = wide_posterior, off_grid
 
 
-def run_workload(spec, args, steps, warmup, rank, device, use_pg, world, S, K):
+def run_workload(spec, args, steps, warmup, rank, device, use_pg, world, S, K, events=True):
     """Builds the workload's inputs in HBM, ramps the clocks, runs `warmup` untimed and `steps` timed steps
-    (barrier + device synchronise on both sides), and returns the measurements of THIS rank plus what the
-    roofline objects need.  One step = one pass of the hot path over the whole batch."""
+    (barrier + device synchronise on both sides), and returns the measurements of THIS rank, the outputs of the
+    last timed step and, with `events`, the HIP-event kernel times the roofline objects need.  One step = one pass
+    of the hot path over the whole batch."""
     import ctypes as C
 
     import torch
@@ -355,16 +384,16 @@ def run_workload(spec, args, steps, warmup, rank, device, use_pg, world, S, K):
         ws = ctx._workspace()
 
     def launch(slot, mid_event=None):
+        """One step; returns what a caller of the path receives: (sums [3] f64, q [n, 5], nll_kl [n, 2])."""
         sums = outs[slot][0]
         if spec.exact:
             # the strictly-float32 encoder: layer-wise v_mfma_f32_16x16x4_f32 GEMMs (activations through HBM),
             # then the ELBO kernel on its heads -- the path vi_fwd(range_check=True) falls back to
-            s2, _, _ = ctx.vi_fwd_exact(ew, x, mask, prior, S, K, seed=1, voxel0=voxel0)
+            s2, q2, nk2 = ctx.vi_fwd_exact(ew, x, mask, prior, S, K, seed=1, voxel0=voxel0)
             sums.copy_(s2)
-            return sums
+            return sums, q2, nk2
         if not two_launch:
-            ctx.vi_fwd(ew, x, mask, prior, S, K, seed=1, voxel0=voxel0, out=outs[slot])
-            return sums
+            return ctx.vi_fwd(ew, x, mask, prior, S, K, seed=1, voxel0=voxel0, out=outs[slot])
         _lib.check(ctx.lib.qbold_encoder_fused_fwd(ctx.handle, C.byref(ew.shape), ew.fused_ptr(), _ptr(x), _ptr(q_buf),
                                                    _ptr(ls_buf), n, _stream()), "qbold_encoder_fused_fwd")
         if mid_event is not None:
@@ -372,14 +401,14 @@ def run_workload(spec, args, steps, warmup, rank, device, use_pg, world, S, K):
         _lib.check(ctx.lib.qbold_elbo_fwd_logsigma(ctx.handle, _ptr(x), _ptr(mask), _ptr(q_buf), _ptr(prior),
                                                    _ptr(ls_buf), int(S), int(K), 1, int(voxel0), _ptr(nk_buf),
                                                    _ptr(sums), _ptr(ws), n, _stream()), "qbold_elbo_fwd_logsigma")
-        return sums
+        return sums, q_buf, nk_buf
 
     def step(k, mid_event=None):
         slot = k % RING
         if pending[slot] is not None:
             pending[slot].wait()   # stream-level wait: the slot's previous all-reduce has finished
             pending[slot] = None
-        sums = launch(slot, mid_event)
+        sums = launch(slot, mid_event)[0]
         if use_pg:
             pending[slot] = dist.all_reduce(sums, async_op=True)  # sum m*nll, sum kl, sum m
         return sums
@@ -406,9 +435,9 @@ def run_workload(spec, args, steps, warmup, rank, device, use_pg, world, S, K):
         step(k)
     drain()
     fence()
-    # per-launch durations: HIP events on the launch stream
+    # per-launch durations (only when asked for: the roofline objects of --full): HIP events on the launch stream
     every = max(1, min(args.event_every, steps // 5))   # at least five bracketed steps (short runs: every step)
-    evs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) if k % every == 0 else None
+    evs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) if events and k % every == 0 else None
            for k in range(steps)]
     n_allreduce = 0
     t0 = time.perf_counter()
@@ -419,7 +448,8 @@ def run_workload(spec, args, steps, warmup, rank, device, use_pg, world, S, K):
             pending[slot] = None
         if ev is not None:
             ev[0].record()
-        sums = launch(slot, ev[1] if (two_launch and ev is not None) else None)
+        result = launch(slot, ev[1] if (two_launch and ev is not None) else None)
+        sums = result[0]
         if ev is not None:
             ev[2].record()
         if use_pg:
@@ -429,11 +459,12 @@ def run_workload(spec, args, steps, warmup, rank, device, use_pg, world, S, K):
     fence()
     elapsed = time.perf_counter() - t0
     evs = [ev for ev in evs if ev is not None]
-    step_kernel_ms = float(np.mean([ea.elapsed_time(eb) for ea, em, eb in evs]))
-    enc_kernel_ms = float(np.mean([ea.elapsed_time(em) for ea, em, eb in evs])) if two_launch else None
+    step_kernel_ms = float(np.mean([ea.elapsed_time(eb) for ea, em, eb in evs])) if evs else None
+    enc_kernel_ms = float(np.mean([ea.elapsed_time(em) for ea, em, eb in evs])) if (evs and two_launch) else None
     s = sums.cpu().numpy()
     return dict(params=params, w=w, T=T, U=U, L=L, n=n, two_launch=two_launch, elapsed=elapsed,
-                step_kernel_ms=step_kernel_ms, enc_kernel_ms=enc_kernel_ms, sums=s, n_allreduce=n_allreduce)
+                step_kernel_ms=step_kernel_ms, enc_kernel_ms=enc_kernel_ms, sums=s, n_allreduce=n_allreduce,
+                outputs={"sums": sums, "q": result[1], "nll_kl": result[2]})
 
 
 # Issue cost of one wave64 vector instruction on gfx950, cycles, measured with scripts/ubench/ubench*.hip (MEASUREMENTS.md 4.4):
@@ -615,16 +646,28 @@ def main():
     ap.add_argument("--rehearse_launch", action="store_true",
                     help="run the N-rank launcher, rendezvous, all-reduce ring and JSON line with no kernel in the step "
                          "(host tensors over gloo; reports no throughput) -- the CPU-container check of --gpus N")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: HIP-event kernel times and the roofline object, "
+                         "the variant workloads and the training step (N = 1 headline workload), the CPU baselines "
+                         "(N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step returned (sums, q, nll_kl) as DIR/<name>.npy "
+                         f"(rank 0; float32 / float64, at most {DUMP_LIMIT_BYTES >> 20} MB: a fixed, seeded sample of "
+                         "voxels when the batch is larger)")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no_variants", action="store_true",
-                    help="skip the variant workloads the default N = 1 headline run times after the headline")
-    ap.add_argument("--variants", action="store_true", help="time the variant workloads even on a non-default run")
+                    help="--full without the variant workloads and the training step")
+    ap.add_argument("--variants", action="store_true",
+                    help="time the variant workloads even on a non-default run (implies --full)")
     ap.add_argument("--variant_steps", type=int, default=20)
     ap.add_argument("--event_every", type=int, default=8,
                     help="HIP events bracket every M-th timed step (a timing event is a barrier packet in the queue: "
                          "around every step they cost up to 5 %% of a 0.5 ms step on some boxes)")
     ap.add_argument("--cpu_budget_s", type=float, default=15.0)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    args.full = args.full or args.variants
     if os.environ.get("QBOLD_DEBUG_SKIP", "0") not in ("", "0"):
         # The default build of the library has no ablation hook at all (they compile in only with -DQBOLD_ABLATION,
         # scripts/dev/build_ablation.sh); with such a build loaded, the run is marked so that the phases switched
@@ -669,11 +712,15 @@ def main():
 
     S, K = args.mc_samples, args.kl_samples
     spec = Spec(args.config, args.protocol, args.voxels, args.encoder_precision, args.tissue, args.exact_f32)
-    m = run_workload(spec, args, args.steps, args.warmup, rank, device, use_pg, world, S, K)
+    m = run_workload(spec, args, args.steps, args.warmup, rank, device, use_pg, world, S, K, events=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["outputs"])
+    del m["outputs"]
     n, T = m["n"], m["T"]
     kernel_ms = m["enc_kernel_ms"] if m["two_launch"] else m["step_kernel_ms"]   # the dominant kernel's launch
     # every rank's own wall time and kernel time; the step time of the job is the MAX over ranks
-    mine = torch.tensor([m["elapsed"] / args.steps * 1e3, kernel_ms], dtype=torch.float64, device=device)
+    mine = torch.tensor([m["elapsed"] / args.steps * 1e3, kernel_ms if args.full else 0.0], dtype=torch.float64,
+                        device=device)
     per_rank = [torch.zeros_like(mine) for _ in range(world)]
     if use_pg:
         dist.all_gather(per_rank, mine)
@@ -710,12 +757,13 @@ def main():
             "backend": (dist.get_backend() + (" (RCCL)" if dist.get_backend() == "nccl" else "")) if use_pg else "none",
             **({"allreduce_per_timed_step": m["n_allreduce"] / args.steps} if use_pg else {}),
             "rank_ms_per_step": {"min": float(per_rank[:, 0].min()), "max": float(per_rank[:, 0].max())},
-            "rank_kernel_ms": {"min": float(per_rank[:, 1].min()), "max": float(per_rank[:, 1].max())},
+            **({"rank_kernel_ms": {"min": float(per_rank[:, 1].min()), "max": float(per_rank[:, 1].max())}}
+               if args.full else {}),
             **({"ablation": "QBOLD_DEBUG_SKIP=" + os.environ["QBOLD_DEBUG_SKIP"] + " (NOT a benchmark result)"}
                if os.environ.get("QBOLD_DEBUG_SKIP", "0") not in ("", "0") else {}),
-            "roofline": roofline_of(spec, m, S, K, m["step_kernel_ms"], kernel_ms),
+            **({"roofline": roofline_of(spec, m, S, K, m["step_kernel_ms"], kernel_ms)} if args.full else {}),
         }
-        if world == 1 and (args.variants or (default_headline and not args.no_variants)):
+        if world == 1 and args.full and (args.variants or (default_headline and not args.no_variants)):
             # the other configurations the summaries quote, each timed here like the headline (same ramp, HIP
             # events, barrier-bracketed wall clock) so that every quoted number is in this one line
             vsteps = max(args.variant_steps, 20)
@@ -727,6 +775,7 @@ def main():
                 vs = Spec(**kw)
                 try:
                     vm = run_workload(vs, args, vsteps, min(args.warmup, 5), rank, device, use_pg, world, S, K)
+                    del vm["outputs"]
                 except Exception as e:   # a variant never takes the headline down
                     line["variants"][name] = {"error": repr(e)}
                     continue
@@ -757,7 +806,7 @@ def main():
                     config_dir=os.path.join(os.path.dirname(os.path.abspath(__file__)), "config"))
             except Exception as e:
                 line["training_step"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(m["params"], m["w"], S, K, args.cpu_budget_s)
         print(json.dumps(line), flush=True)
     if use_pg:

@@ -19,7 +19,7 @@ prof() {   # prof <out dir> <rocprof args...> -- <bench args...>
     local out=$1; shift
     local rargs=(); while [ "$1" != "--" ]; do rargs+=("$1"); shift; done; shift
     rm -rf $out; mkdir -p $out
-    (cd /tmp && rocprofv3 "${rargs[@]}" --output-format csv -d $out -- python3 $R/bench.py "$@" --no_cpu_baseline --no_variants > $out/bench.log 2>&1) \
+    (cd /tmp && rocprofv3 "${rargs[@]}" --output-format csv -d $out -- python3 $R/bench.py "$@" --full --no_cpu_baseline --no_variants > $out/bench.log 2>&1) \
         || echo "FAILED: $out"
     echo "done $(basename $out) $(date +%T)"
 }
@@ -37,7 +37,7 @@ if [ "$PART" = a ]; then
     cp $D/trace/*/*_kernel_stats.csv $P/r04_kernel_stats.csv
     python3 scripts/summarise_prof.py $D vi_fwd > $P/r04_vi_fwd_summary.json
     grep -h '"metric"' $D/trace/bench.log | tail -1 > $P/r04_bench_under_rocprof.json
-    python3 bench.py > $P/r04_bench.json 2> $G/r04_bench.err; echo "bench default rc=$?"
+    python3 bench.py --full > $P/r04_bench.json 2> $G/r04_bench.err; echo "bench default rc=$?"
 elif [ "$PART" = c ]; then
     D=$G/prof_r04train
     rm -rf $D; mkdir -p $D
@@ -69,7 +69,7 @@ else
         prof $D/pmc_write --pmc WRITE_SIZE -- --steps 20 --warmup 5 $args
         python3 scripts/summarise_prof.py $D vi_fwd > $P/r04_${tag}_vi_fwd_summary.json
     done
-    python3 bench.py --config 3 --no_cpu_baseline > $P/r04_bench_config3.json 2> $G/r04_bench_c3.err; echo "bench config3 rc=$?"
+    python3 bench.py --config 3 --full --no_cpu_baseline > $P/r04_bench_config3.json 2> $G/r04_bench_c3.err; echo "bench config3 rc=$?"
 fi
 python3 -c "import json; from qbold_vi_amd.build import file_digests; print(json.dumps(file_digests()))" > $P/source_sha256_$PART.txt
 ls -la $P

@@ -281,7 +281,7 @@ def test_self_launched_two_ranks_on_one_card():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--voxels", "65536", "--ramp_ms", "20"],
+                        "--voxels", "65536", "--ramp_ms", "20", "--full"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
@@ -295,9 +295,9 @@ def test_self_launched_two_ranks_on_one_card():
 
 @pytest.mark.gpu
 def test_driver_command_line_carries_every_variant():
-    """The driver's own N = 1 command: headline keys unchanged, and the variants object beside them."""
+    """The driver's N = 1 command with --full: headline keys unchanged, and the variants object beside them."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--cpu_budget_s", "1"], capture_output=True, text=True, cwd=ROOT, timeout=1200)
+                        "--cpu_budget_s", "1", "--full"], capture_output=True, text=True, cwd=ROOT, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -310,7 +310,7 @@ def test_driver_command_line_carries_every_variant():
 @pytest.mark.gpu
 def test_live_bench_line_keeps_the_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--voxels",
-                        "65536", "--ramp_ms", "20", "--cpu_budget_s", "1"],
+                        "65536", "--ramp_ms", "20", "--cpu_budget_s", "1", "--full"],
                        capture_output=True, text=True, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -318,3 +318,70 @@ def test_live_bench_line_keeps_the_contract():
     d = json.loads(lines[0])
     check_line(d, expect_cpu_baseline=True)
     assert d["steps"] == 5 and d["warmup"] == 2 and d["n_gpus"] == 1
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("qbold_bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_samples_the_same_voxels_of_every_array(tmp_path):
+    """--dump-outputs over its size limit: one fixed, seeded sample of rows, the same rows in every per-voxel array,
+    the same sample on every run; the sums are written whole, in float64."""
+    torch = pytest.importorskip("torch")
+    import numpy as np
+    bench = _load_bench()
+    n = 1000
+    ids = torch.arange(n, dtype=torch.float32)
+    outputs = {"sums": torch.tensor([1.0, 2.0, 3.0], dtype=torch.float64),
+               "q": ids[:, None].repeat(1, 5).contiguous(), "nll_kl": ids[:, None].repeat(1, 2).contiguous()}
+    limit = 4096 + 100 * 7 * 4
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outputs, limit=limit)
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in outputs}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in outputs}
+    assert a["sums"].dtype == np.float64 and list(a["sums"]) == [1.0, 2.0, 3.0]
+    assert a["q"].dtype == np.float32 and a["q"].shape == (100, 5) and a["nll_kl"].shape == (100, 2)
+    rows = a["q"][:, 0]
+    assert (np.diff(rows) > 0).all() and (a["nll_kl"][:, 0] == rows).all() and (a["q"] == rows[:, None]).all()
+    assert all((a[k] == b[k]).all() for k in outputs)
+    assert sum(a[k].nbytes for k in a) <= limit
+    bench.dump_outputs(str(tmp_path / "whole"), outputs)    # under the default limit: every row
+    assert np.load(tmp_path / "whole" / "q.npy").shape == (n, 5)
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the headline keys and none of what --full adds;
+    --dump-outputs writes the last timed step's sums, q and nll_kl, identical on a second run with the same arguments."""
+    import numpy as np
+    n = 65536
+    runs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup",
+                            "2", "--voxels", str(n), "--ramp_ms", "20", "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, cwd=ROOT, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1
+        runs.append(lines[0])
+    d = runs[0]
+    for k in TOP:
+        if k != "roofline":
+            assert k in d, k
+    for k in ("roofline", "variants", "training_step", "cpu_baseline", "rank_kernel_ms"):
+        assert k not in d, k
+    assert d["metric"] == "voxel-ELBO evals/sec" and d["unit"] == "voxel-ELBO evals/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1
+    assert abs(d["value"] - n * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    out = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("sums", "q", "nll_kl")}
+    assert out["sums"].dtype == np.float64 and out["sums"].shape == (3,)
+    assert out["q"].dtype == np.float32 and out["q"].shape == (n, 5) and out["nll_kl"].shape == (n, 2)
+    assert np.isfinite(out["q"]).all() and np.isfinite(out["nll_kl"]).all()
+    assert out["sums"][2] == n and abs((out["sums"][0] + out["sums"][1]) / out["sums"][2] - d["neg_elbo"]) < 1e-12
+    for k, v in out.items():
+        assert (np.load(tmp_path / "b" / f"{k}.npy") == v).all(), k
+    assert runs[1]["neg_elbo"] == d["neg_elbo"]
