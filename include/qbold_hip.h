@@ -311,7 +311,8 @@ int qbold_kl_diag(const qbold_ctx* ctx, const float* q, const float* prior, cons
                   float* g_q, double* sums, void* workspace, int64_t N, void* stream);
 
 /* The counter-based normal stream the fused kernels consume: z [N][n][2] for global voxels
- * voxel0 .. voxel0+N-1; stream_id 0 = likelihood draws, 1 = KL draws, 2 = moments, 3 = noise.
+ * voxel0 .. voxel0+N-1; stream_id 0 = likelihood draws, 1 = KL draws, 2 = moments, 3 = noise, 6 = the importance
+ * draws of qbold_log_evidence_fwd (4 is qbold_kl_mog's, 5 the dropout masks').
  * Replaces tf.random.normal at model.py:25 with a reproducible, sharding-invariant generator
  * (Random123 Philox4x32-7, four draws per call: draw i = word i & 3 of call i >> 2 keyed (voxel, call, stream_id; seed);
  * Box-Muller on the word's low sixteen bits (radius, u1 = (lo + 0.5) 2^-16, so |z| <= 4.8549) and top 23 bits (angle,
@@ -364,6 +365,21 @@ int qbold_vi_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* shape, const f
                  const float* x, const float* mask, const float* prior, int S, int K, uint64_t seed,
                  int64_t voxel0, float* q_out, float* nll_kl, double* sums, void* workspace,
                  int64_t N, void* stream);
+
+/* Importance-weighted evidence (Burda et al. 2016) of the fine-tuning model (model.py:239-286, 527-568, 592-610):
+ * per voxel K draws z_k ~ q, log w_k = -nll(x|z_k) - log q(z_k) + log prior(z_k) on the SAME draw.
+ *   out [N][3] = (log p^ = logsumexp log w - log K, mean_k log w (the same-draw ELBO), ESS = (sum w)^2 / sum w^2)
+ *   is_means [N][3] or NULL: self-normalised posterior means of (OEF, DBV, R2') (calculate_means' columns)
+ *   z: explicit normals [N][K][2] or NULL for the Philox stream 6 (seed, voxel0 + i): qbold_normals(seed, 6, ...)
+ *   sums: DEVICE double[3] = (sum_{m>0} m (-log p^), sum_{m>0} m (-ELBO_same), sum m), overwritten
+ *   workspace: qbold_elbo_workspace_bytes() bytes; x, mask, q, prior, sigma, stream as qbold_elbo_fwd.
+ * The use_mvg = True family: configurations qbold_elbo_fwd accepts; QBOLD_ERR_UNSUPPORTED otherwise.
+ * QBOLD_ERR_INVALID for K < 1, K > QBOLD_IW_MAX_K (2 K must index the explicit normals with 32 bits) or NULL out. */
+#define QBOLD_IW_MAX_K (1 << 30)
+int qbold_log_evidence_fwd(const qbold_ctx* ctx, const float* x, const float* mask, const float* q,
+                           const float* prior, const float* sigma, const float* z, int K, uint64_t seed,
+                           int64_t voxel0, float* out, float* is_means, double* sums, void* workspace,
+                           int64_t N, void* stream);
 
 /* ---- gradients (training) ------------------------------------------------------------------- */
 /* Adjoint of qbold_elbo_fwd with respect to the encoder's head outputs: what TensorFlow autodiff

@@ -111,3 +111,11 @@ def elbo_from_sums(sums):
     nll = sums[0] / sums[2]
     kl = sums[1] / sums[2]
     return nll, kl, nll + kl
+
+
+def log_evidence_from_sums(sums):
+    """(mean log p^, mean same-draw ELBO, mean gap) from the reduced sums of qbold_log_evidence_fwd: the sums are
+    masked as the ELBO's and go through the same all-reduce (allreduce_sums)."""
+    lp = -sums[0] / sums[2]
+    el = -sums[1] / sums[2]
+    return lp, el, lp - el

@@ -246,6 +246,42 @@ class FineTuner:
         return dict(sums=sums, q=q, nll_kl=nll_kl, nll=sums[0] / sums[2], kl=sums[1] / sums[2],
                     elbo=(sums[0] + sums[1]) / sums[2])
 
+    def log_evidence(self, data, mask, prior, no_samples=100, seed=1, voxel0=0, want_means=False):
+        """Importance-weighted evidence (Burda et al. 2016) of `no_samples` = K draws per voxel from the fitted
+        posterior, on the encoder heads of encoder_model.predict (as the spatial branch of elbo() takes them) and the
+        homoscedastic sigma when the fine tuner carries one.  Per voxel, shaped like the data's spatial dims:
+          log_evidence  log p^ = logsumexp_k log w_k - log K  (>= elbo; -> log p(x) as K grows)
+          elbo          mean_k log w_k: the ELBO of the SAME draws (log w = -nll - log q + log prior)
+          ess           (sum w)^2 / sum w^2 in [1, K]: how well q covers the posterior
+          is_means      [..., 3] self-normalised posterior means of (OEF, DBV, R2') (want_means) or None
+        and the masked sums (distributed.allreduce_sums reduces them across shards) with mean_log_evidence,
+        mean_elbo and gap = mean_log_evidence - mean_elbo (an estimate of the mean KL(q || p(z | x)))."""
+        from .distributed import log_evidence_from_sums
+        tr = self._trainer
+        if not tr._use_mvg:
+            raise NotImplementedError(
+                "log_evidence evaluates the use_mvg=True family (the logit-MVN of transform_std / transform_offdiag); "
+                "the diagonal family draws with exp(raw_s), not transform_std (model.py:696-698), so it is a "
+                "different density")
+        if self.pop_prior is not None:
+            raise NotImplementedError("log_evidence needs a per-voxel prior; the population prior is not built for it")
+        T = data.shape[-1]
+        x = _flat(data, T)
+        m = None if mask is None else mask.reshape(-1)
+        p5 = _flat(prior, prior.shape[-1]).contiguous()
+        _, q5, sg5 = self.encoder_model.predict(data, want=("out2", "sigma"))
+        q = _flat(q5, q5.shape[-1]).contiguous()
+        sg = _flat(sg5, T)
+        if self.log_sigma is not None:   # the encoder's sigma head is not part of this model (model.py:277-281)
+            sg = torch.full_like(sg, math.exp(self.log_sigma))
+        sums, out, means = tr._ctx.log_evidence(x, m, q, p5, sg, no_samples, seed=seed, voxel0=voxel0,
+                                                want_means=want_means)
+        lead = data.shape[:-1]
+        lp, el, gap = log_evidence_from_sums(sums)
+        return dict(log_evidence=out[:, 0].reshape(lead), elbo=out[:, 1].reshape(lead), ess=out[:, 2].reshape(lead),
+                    is_means=None if means is None else means.reshape(lead + (3,)), sums=sums,
+                    mean_log_evidence=lp, mean_elbo=el, gap=gap)
+
 
 class EncoderTrainer:
     def __init__(self,
@@ -593,11 +629,14 @@ class EncoderTrainer:
         return tuple(out)
 
     def save_predictions(self, model, data, filename, transform_directory=None, use_first_op=True,
-                         fine_tuner_model=None, priors=None):
+                         fine_tuner_model=None, priors=None, iw_samples=None):
         """model.py:772-887: write `<filename>_{oef,dbv,r2p,logstds}.nii.gz` (posterior means of
         OEF / DBV / R2' over 200 draws and their variances) and, with a fine tuner,
         `_likelihood` (per-voxel NLL averaged over 100 stochastic passes), `_kl` (100-draw KL to
         `priors`) and `_residual` (mean |normalised data - one sampled prediction|).
+        iw_samples = K (with a fine tuner; this package's addition): also `_logevidence` (importance-weighted
+        log p^ of K draws, FineTuner.log_evidence), `_vigap` (log p^ - the same draws' ELBO) and `_ess` (effective
+        sample size), zero outside the mask; the three maps [subj, X, Y, Z, 1] are returned as a dict.
         data [subj, X, Y, Z, T+1] with the mask last; each map is stored as [X, Y, Z, subj*C].
         `transform_directory/example.nii.gz`, when present, donates its header (:794-797); the
         FSL `applywarp`/`fslmerge` MNI step (:850-879) is preprocessing outside this package and
@@ -645,7 +684,21 @@ class EncoderTrainer:
             y_pred = y_pred / (y_pred[..., sl].mean(-1, keepdim=True) + 1e-3)
             save_im_data((y_true - y_pred).abs().mean(-1, keepdim=True), filename + '_residual')
 
+        iw_maps = None
+        if fine_tuner_model and iw_samples:
+            iw = fine_tuner_model.log_evidence(data[..., :-1], mask,
+                                               torch.as_tensor(priors, device=data.device)[..., :self._nq],
+                                               no_samples=int(iw_samples), seed=self._seed + 31)
+            live = mask[..., 0] > 0
+            zero = torch.zeros_like(iw["log_evidence"])
+            iw_maps = {k: torch.where(live, v, zero)[..., None] for k, v in
+                       (("logevidence", iw["log_evidence"]), ("vigap", iw["log_evidence"] - iw["elbo"]),
+                        ("ess", iw["ess"]))}
+            for k, v in iw_maps.items():
+                save_im_data(v, filename + '_' + k)
+
         save_im_data(means[..., 0:1], filename + '_oef')
         save_im_data(means[..., 1:2], filename + '_dbv')
         save_im_data(means[..., 2:3], filename + '_r2p')
         save_im_data(log_stds, filename + '_logstds')
+        return iw_maps

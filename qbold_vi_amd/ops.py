@@ -441,6 +441,28 @@ class Context:
                                            _ptr(self._workspace()), N, _stream()), "qbold_elbo_fwd")
         return sums, out
 
+    def log_evidence(self, x, mask, q, prior, sigma, K=100, z=None, seed=1, voxel0=0, want_means=False):
+        """Importance-weighted evidence of K draws per voxel (qbold_log_evidence_fwd; Philox stream 6 unless z
+        [N, K, 2] is given).  Returns (sums double[3] device tensor = (sum [m>0] m (-log p^), sum [m>0] m (-ELBO_same),
+        sum m), out [N, 3] = (log p^, same-draw ELBO, ESS), is_means [N, 3] = self-normalised (OEF, DBV, R2') or None)."""
+        x = _f32(x, "x", self.T)
+        N = x.numel() // self.T
+        q = _f32(q, "q", 5)
+        prior = _f32(prior, "prior", 5)
+        sigma = _f32(sigma, "sigma", self.T)
+        mask = _f32(mask, "mask") if mask is not None else None
+        z = _f32(z, "z", 2) if z is not None else None
+        if z is not None and z.numel() != N * K * 2:
+            raise ValueError("z must be [N, K, 2]")
+        sums = torch.empty(3, dtype=torch.float64, device=x.device)
+        out = torch.empty((N, 3), dtype=torch.float32, device=x.device)
+        means = torch.empty((N, 3), dtype=torch.float32, device=x.device) if want_means else None
+        _lib.check(self.lib.qbold_log_evidence_fwd(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior),
+                                                   _ptr(sigma), _ptr(z), int(K), int(seed), int(voxel0), _ptr(out),
+                                                   _ptr(means), _ptr(sums), _ptr(self._workspace()), N, _stream()),
+                   "qbold_log_evidence_fwd")
+        return sums, out, means
+
     def vi_fwd_exact(self, weights, x, mask, prior, S=1, K=70, seed=1, voxel0=0):
         """The same evaluation with the encoder on the exact-float32 layer-wise path (f32-input MFMA GEMMs,
         qbold_encoder_train_fwd) -- no f16 operand split, so no 65504 operand limit.  Slow (one launch per layer,

@@ -63,6 +63,11 @@ def main():
         "kl_diag(+grad)": (lambda: ctx.kl_diag(q, o1, mask, g_q=gq0), 44 + 40),
         "elbo_fwd(S=32,K=70)": (lambda: ctx.elbo_fwd(x, mask, q, o1, sg, 32, 70, seed=1), 8 * T + 52),
         "elbo_bwd(S=1,K=70)": (lambda: ctx.elbo_bwd(x, mask, q, o1, ls, 1, 70, seed=1), 12 * T + 72),
+        # importance-weighted evidence against the ELBO kernel on the same draws' forward-model work (S = K = K_iw)
+        "log_evidence(K=64)": (lambda: ctx.log_evidence(x, mask, q, o1, sg, 64, seed=1), 8 * T + 52),
+        "elbo_fwd(S=64,K=64)": (lambda: ctx.elbo_fwd(x, mask, q, o1, sg, 64, 64, seed=1), 8 * T + 52),
+        "log_evidence(K=1024)": (lambda: ctx.log_evidence(x, mask, q, o1, sg, 1024, seed=1), 8 * T + 52),
+        "elbo_fwd(S=1024,K=1024)": (lambda: ctx.elbo_fwd(x, mask, q, o1, sg, 1024, 1024, seed=1), 8 * T + 52),
         "vi_fwd(S=32,K=70)": (lambda: ctx.vi_fwd(ew, x, mask, o1, 32, 70, seed=1), 4 * T + 52),
         "synth_loss_bwd": (lambda: st.synth_loss_bwd(y3, o1), 12 + 20 + 24),
         "wls_fit": (lambda: ctx.wls_fit(x), 4 * T + 12),
