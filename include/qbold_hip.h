@@ -312,7 +312,8 @@ int qbold_kl_diag(const qbold_ctx* ctx, const float* q, const float* prior, cons
 
 /* The counter-based normal stream the fused kernels consume: z [N][n][2] for global voxels
  * voxel0 .. voxel0+N-1; stream_id 0 = likelihood draws, 1 = KL draws, 2 = moments, 3 = noise, 6 = the importance
- * draws of qbold_log_evidence_fwd (4 is qbold_kl_mog's, 5 the dropout masks').
+ * draws of qbold_log_evidence_fwd, 7 = the refinement draws of qbold_refine_posterior (4 is qbold_kl_mog's, 5 the
+ * dropout masks').
  * Replaces tf.random.normal at model.py:25 with a reproducible, sharding-invariant generator
  * (Random123 Philox4x32-7, four draws per call: draw i = word i & 3 of call i >> 2 keyed (voxel, call, stream_id; seed);
  * Box-Muller on the word's low sixteen bits (radius, u1 = (lo + 0.5) 2^-16, so |z| <= 4.8549) and top 23 bits (angle,
@@ -380,6 +381,34 @@ int qbold_log_evidence_fwd(const qbold_ctx* ctx, const float* x, const float* ma
                            const float* prior, const float* sigma, const float* z, int K, uint64_t seed,
                            int64_t voxel0, float* out, float* is_means, double* sums, void* workspace,
                            int64_t N, void* stream);
+
+/* Semi-amortised inference (Kim et al. 2018; Cremer et al. 2018): refine each voxel's posterior, starting from given
+ * encoder heads, by `steps` gradient steps on that voxel's own objective
+ *   E_q[nll(x | y)] + KL(q || prior)   (exact closed-form KL of the logit-space Gaussians, sigma fixed, no TV term)
+ * -- what a Python loop of qbold_elbo_bwd + qbold_adamw_step on the N x 5 heads would do, in one launch with the
+ * voxel's data, heads and optimiser state in registers.  This package's addition; the reference has no counterpart.
+ *   q_in, q_out [N][5]: raw heads (the encoder's parameterisation, transform_std / transform_offdiag); q_out may alias
+ *     q_in.  Voxels with mask <= 0 (or NaN) get q_in copied bit for bit; mask NULL refines every voxel.
+ *   sigma [N][T]: the exponentiated sigma, as qbold_elbo_fwd takes it.
+ *   Per step j: S reparameterised likelihood draws; the gradient of their mean NLL plus the exact gradient of the
+ *     closed-form KL (the expectation of the Monte-Carlo KL gradient while the logit clip does not bind), then Adam
+ *     (bias-corrected) or SGD at lr_j = lr_final + (lr - lr_final)(1 + cos(pi j / steps)) / 2.
+ *   z: explicit normals [N][steps][Sp][2], Sp = 4 ceil(S / 4) (draws S .. Sp - 1 of a step unused), or NULL for the
+ *     Philox stream 7 keyed by the global voxel: step j's draw d is draw j Sp + d of qbold_normals(seed, 7, voxel0,
+ *     steps Sp), so results do not depend on the sharding.
+ *   loss [N][2] or NULL: the Monte-Carlo -ELBO (mean NLL of the step's draws + closed-form KL) at step 0 and its mean
+ *     over the last ceil(steps / 10) steps; 0 for masked voxels.
+ * Full signal model in table mode, T = 11 or 24 (qbold_elbo_bwd's configurations); QBOLD_ERR_UNSUPPORTED otherwise.
+ * QBOLD_ERR_INVALID for steps < 1, S < 1, steps Sp / 4 >= 2^32 (the Philox call word), lr <= 0, lr_final < 0, Adam
+ * betas outside [0, 1) or eps <= 0, an optimizer other than 0 / 1, or a NULL required buffer. */
+typedef struct {
+    int optimizer; /* 0 Adam, 1 SGD */
+    float lr, lr_final, beta1, beta2, eps;
+} qbold_refine_cfg;
+int qbold_refine_posterior(const qbold_ctx* ctx, const float* x, const float* mask, const float* q_in,
+                           const float* prior, const float* sigma, const float* z, int steps, int S,
+                           const qbold_refine_cfg* cfg, uint64_t seed, int64_t voxel0,
+                           float* q_out, float* loss, int64_t N, void* stream);
 
 /* ---- gradients (training) ------------------------------------------------------------------- */
 /* Adjoint of qbold_elbo_fwd with respect to the encoder's head outputs: what TensorFlow autodiff

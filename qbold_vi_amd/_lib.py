@@ -40,6 +40,12 @@ class EncoderShape(C.Structure):
                 ("layer_norm", C.c_int32), ("dropout_rate", C.c_float), ("dropout_seed", C.c_uint64)]
 
 
+class RefineCfg(C.Structure):
+    """qbold_refine_cfg: optimizer 0 = Adam, 1 = SGD; the learning rate follows a cosine from lr to lr_final."""
+    _fields_ = [("optimizer", C.c_int32), ("lr", C.c_float), ("lr_final", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("eps", C.c_float)]
+
+
 class Geometry(C.Structure):
     """qbold_geometry: a [B][X][Y][Z][C] crop batch."""
     _fields_ = [("B", C.c_int32), ("X", C.c_int32), ("Y", C.c_int32), ("Z", C.c_int32)]
@@ -116,6 +122,8 @@ SIGNATURES = {
     "qbold_adamw_step": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double,
                                    C.c_double, C.c_double, _I64, _P]),
     "qbold_log_evidence_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
+    "qbold_refine_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(RefineCfg), _U64,
+                                         _I64, _P, _P, _I64, _P]),
     "qbold_vi_fwd": (C.c_int, [_P, C.POINTER(EncoderShape), _P, _P, _P, _P, C.c_int, C.c_int,
                                _U64, _I64, _P, _P, _P, _P, _I64, _P]),
 }

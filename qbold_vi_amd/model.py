@@ -189,7 +189,7 @@ class FineTuner:
         # 'predictions' is the S-fold tiled distribution, as in the reference (model.py:245,285)
         return {'predictions': qs, 'predicted_images': torch.cat([output, sig], -1)}
 
-    def elbo(self, data, mask, prior, no_samples=None, kl_samples=70, seed=1, voxel0=0, kl_tiled=None):
+    def elbo(self, data, mask, prior, no_samples=None, kl_samples=70, seed=1, voxel0=0, kl_tiled=None, q=None):
         """The fused path: one launch for encoder + S draws + forward model + NLL + K-draw KL
         (image crops: spatial encoder, then the ELBO kernel).
         Returns dict(nll, kl, elbo (= nll + kl, train.py:351), sums, q, nll_kl).
@@ -198,7 +198,10 @@ class FineTuner:
         reference tiles the batch S-fold (model.py:245-246, 656) and kl_loss draws `kl_samples` KL samples per TILED
         row, i.e. S * kl_samples draws per voxel, averaged (model.py:592-610, 661-663).  The kernels never tile; the
         same estimator is S * kl_samples in-kernel draws per voxel.  kl_tiled=False draws kl_samples per voxel
-        whatever S (same expectation, S times fewer draws: round 1's behaviour)."""
+        whatever S (same expectation, S times fewer draws: round 1's behaviour).
+
+        q (this package's addition): heads [..., C] to score instead of the encoder's (refine()'s output, say), with
+        the encoder's sigma head or the fine tuner's homoscedastic sigma; None scores the encoder's heads."""
         tr = self._trainer
         S = tr._no_samples if no_samples is None else no_samples
         kl_samples = tr.kl_draws(kl_samples, S, kl_tiled)
@@ -209,9 +212,9 @@ class FineTuner:
         mog = self.pop_prior is not None and self.pop_prior.size > 4
         if self.pop_prior is not None and not mog:   # the per-voxel prior is ignored (model.py:687-690): one population prior
             p5 = _pad5(torch.as_tensor(self.pop_prior, device=x.device).expand(x.shape[0], 4)).contiguous()
-        if tr._is_spatial(data) or self.log_sigma is not None:
+        if q is not None or tr._is_spatial(data) or self.log_sigma is not None:
             _, q5, sg5 = self.encoder_model.predict(data, want=("out2", "sigma"))
-            q = _pad5(_flat(q5, q5.shape[-1])).contiguous()
+            q = _pad5(_flat(q5 if q is None else q, q5.shape[-1])).contiguous()
             sg = _flat(sg5, x.shape[-1])
             if self.log_sigma is not None:   # the encoder's sigma head is not part of this model (model.py:277-281)
                 sg = torch.full_like(sg, math.exp(self.log_sigma))
@@ -246,7 +249,7 @@ class FineTuner:
         return dict(sums=sums, q=q, nll_kl=nll_kl, nll=sums[0] / sums[2], kl=sums[1] / sums[2],
                     elbo=(sums[0] + sums[1]) / sums[2])
 
-    def log_evidence(self, data, mask, prior, no_samples=100, seed=1, voxel0=0, want_means=False):
+    def log_evidence(self, data, mask, prior, no_samples=100, seed=1, voxel0=0, want_means=False, q=None):
         """Importance-weighted evidence (Burda et al. 2016) of `no_samples` = K draws per voxel from the fitted
         posterior, on the encoder heads of encoder_model.predict (as the spatial branch of elbo() takes them) and the
         homoscedastic sigma when the fine tuner carries one.  Per voxel, shaped like the data's spatial dims:
@@ -255,25 +258,16 @@ class FineTuner:
           ess           (sum w)^2 / sum w^2 in [1, K]: how well q covers the posterior
           is_means      [..., 3] self-normalised posterior means of (OEF, DBV, R2') (want_means) or None
         and the masked sums (distributed.allreduce_sums reduces them across shards) with mean_log_evidence,
-        mean_elbo and gap = mean_log_evidence - mean_elbo (an estimate of the mean KL(q || p(z | x)))."""
+        mean_elbo and gap = mean_log_evidence - mean_elbo (an estimate of the mean KL(q || p(z | x))).
+        q: heads [..., 5] to evaluate instead of the encoder's (refine()'s output, say); sigma as above."""
         from .distributed import log_evidence_from_sums
         tr = self._trainer
-        if not tr._use_mvg:
-            raise NotImplementedError(
-                "log_evidence evaluates the use_mvg=True family (the logit-MVN of transform_std / transform_offdiag); "
-                "the diagonal family draws with exp(raw_s), not transform_std (model.py:696-698), so it is a "
-                "different density")
-        if self.pop_prior is not None:
-            raise NotImplementedError("log_evidence needs a per-voxel prior; the population prior is not built for it")
+        self._check_mvn_family("log_evidence")
         T = data.shape[-1]
         x = _flat(data, T)
         m = None if mask is None else mask.reshape(-1)
         p5 = _flat(prior, prior.shape[-1]).contiguous()
-        _, q5, sg5 = self.encoder_model.predict(data, want=("out2", "sigma"))
-        q = _flat(q5, q5.shape[-1]).contiguous()
-        sg = _flat(sg5, T)
-        if self.log_sigma is not None:   # the encoder's sigma head is not part of this model (model.py:277-281)
-            sg = torch.full_like(sg, math.exp(self.log_sigma))
+        q, sg = self._heads_and_sigma(data, q)
         sums, out, means = tr._ctx.log_evidence(x, m, q, p5, sg, no_samples, seed=seed, voxel0=voxel0,
                                                 want_means=want_means)
         lead = data.shape[:-1]
@@ -281,6 +275,48 @@ class FineTuner:
         return dict(log_evidence=out[:, 0].reshape(lead), elbo=out[:, 1].reshape(lead), ess=out[:, 2].reshape(lead),
                     is_means=None if means is None else means.reshape(lead + (3,)), sums=sums,
                     mean_log_evidence=lp, mean_elbo=el, gap=gap)
+
+    def _check_mvn_family(self, what):
+        if not self._trainer._use_mvg:
+            raise NotImplementedError(
+                f"{what} works on the use_mvg=True family (the logit-MVN of transform_std / transform_offdiag); "
+                "the diagonal family draws with exp(raw_s), not transform_std (model.py:696-698), so it is a "
+                "different density")
+        if self.pop_prior is not None:
+            raise NotImplementedError(f"{what} needs a per-voxel prior; the population prior is not built for it")
+
+    def _heads_and_sigma(self, data, q=None):
+        """Flat heads [N, 5] (the encoder's, or the given q) and the sigma [N, T] that goes with them: the encoder's
+        sigma head, or the fine tuner's homoscedastic sigma when it carries one."""
+        T = data.shape[-1]
+        _, q5, sg5 = self.encoder_model.predict(data, want=("out2", "sigma"))
+        q = _flat(q5 if q is None else torch.as_tensor(q, device=q5.device), q5.shape[-1]).contiguous()
+        sg = _flat(sg5, T)
+        if self.log_sigma is not None:   # the encoder's sigma head is not part of this model (model.py:277-281)
+            sg = torch.full_like(sg, math.exp(self.log_sigma))
+        return q, sg
+
+    def refine(self, data, mask, prior, steps=200, no_samples=1, lr=0.1, lr_final=None, optimizer="adam",
+               seed=1, voxel0=0):
+        """Semi-amortised inference (Kim et al. 2018; Cremer et al. 2018): start from the encoder heads of
+        encoder_model.predict (as log_evidence() takes them) and run `steps` Adam / SGD steps on each voxel's own
+        E_q[nll] + KL(q || prior), `no_samples` likelihood draws per step, sigma held fixed (the encoder's sigma head
+        or the fine tuner's homoscedastic sigma), no TV term (Context.refine_posterior; lr_final None = lr / 10).
+        Voxels outside the mask keep the encoder's heads.  Returns dict(q = refined raw heads shaped like the data's
+        spatial dims + (5,), loss = [..., 2] (-ELBO estimate at the first step, its mean over the last tenth of the
+        steps)); q goes unchanged to calculate_means, elbo(q=...), log_evidence(q=...)."""
+        tr = self._trainer
+        self._check_mvn_family("refine")
+        T = data.shape[-1]
+        x = _flat(data, T)
+        m = None if mask is None else mask.reshape(-1)
+        p5 = _flat(prior, prior.shape[-1]).contiguous()
+        q, sg = self._heads_and_sigma(data)
+        q_out, loss = tr._ctx.refine_posterior(x, m, q, p5, sg, steps=steps, S=no_samples, lr=lr,
+                                               lr_final=lr_final,
+                                               optimizer=optimizer, seed=seed, voxel0=voxel0, want_loss=True)
+        lead = data.shape[:-1]
+        return dict(q=q_out.reshape(lead + (5,)), loss=loss.reshape(lead + (2,)))
 
 
 class EncoderTrainer:
@@ -629,7 +665,7 @@ class EncoderTrainer:
         return tuple(out)
 
     def save_predictions(self, model, data, filename, transform_directory=None, use_first_op=True,
-                         fine_tuner_model=None, priors=None, iw_samples=None):
+                         fine_tuner_model=None, priors=None, iw_samples=None, refine_steps=None):
         """model.py:772-887: write `<filename>_{oef,dbv,r2p,logstds}.nii.gz` (posterior means of
         OEF / DBV / R2' over 200 draws and their variances) and, with a fine tuner,
         `_likelihood` (per-voxel NLL averaged over 100 stochastic passes), `_kl` (100-draw KL to
@@ -637,6 +673,10 @@ class EncoderTrainer:
         iw_samples = K (with a fine tuner; this package's addition): also `_logevidence` (importance-weighted
         log p^ of K draws, FineTuner.log_evidence), `_vigap` (log p^ - the same draws' ELBO) and `_ess` (effective
         sample size), zero outside the mask; the three maps [subj, X, Y, Z, 1] are returned as a dict.
+        refine_steps (with a fine tuner; this package's addition): refine each voxel's heads by that many steps
+        (FineTuner.refine) and also write `_oef_refined`, `_dbv_refined`, `_r2p_refined` (calculate_means of the
+        refined heads) and `_amortgap` (per-voxel ELBO of the refined heads minus that of the encoder's, both from
+        FineTuner.elbo(q=...) on the same draws; zero outside the mask); these maps join the returned dict.
         data [subj, X, Y, Z, T+1] with the mask last; each map is stored as [X, Y, Z, subj*C].
         `transform_directory/example.nii.gz`, when present, donates its header (:794-797); the
         FSL `applywarp`/`fslmerge` MNI step (:850-879) is preprocessing outside this package and
@@ -696,6 +736,27 @@ class EncoderTrainer:
                         ("ess", iw["ess"]))}
             for k, v in iw_maps.items():
                 save_im_data(v, filename + '_' + k)
+
+        if fine_tuner_model and refine_steps:
+            x_ft = data[..., :-1]
+            p_ft = torch.as_tensor(priors, device=data.device)[..., :self._nq]
+            ref = fine_tuner_model.refine(x_ft, mask, p_ft, steps=int(refine_steps), seed=self._seed + 43)
+            q0, _ = fine_tuner_model._heads_and_sigma(x_ft)
+            lead = data.shape[:4]
+
+            def elbo_v(qq):   # per-voxel ELBO = -(nll + kl), the same seed (so the same draws) for both heads
+                e = fine_tuner_model.elbo(x_ft, mask, p_ft, no_samples=32, kl_samples=70, seed=self._seed + 47,
+                                          kl_tiled=False, q=qq)
+                return -(e["nll_kl"][:, 0] + e["nll_kl"][:, 1])
+            live = mask.reshape(-1) > 0
+            gap = elbo_v(ref["q"].reshape(-1, 5)) - elbo_v(q0)
+            gap = torch.where(live, gap, torch.zeros_like(gap))
+            r_means = self.calculate_means(ref["q"], None, include_r2p=True, no_samples=200)
+            ref_maps = {"oef_refined": r_means[..., 0:1], "dbv_refined": r_means[..., 1:2],
+                        "r2p_refined": r_means[..., 2:3], "amortgap": gap.reshape(lead + (1,))}
+            for k, v in ref_maps.items():
+                save_im_data(v, filename + '_' + k)
+            iw_maps = dict(iw_maps or {}, **ref_maps)
 
         save_im_data(means[..., 0:1], filename + '_oef')
         save_im_data(means[..., 1:2], filename + '_dbv')

@@ -463,6 +463,46 @@ class Context:
                    "qbold_log_evidence_fwd")
         return sums, out, means
 
+    def refine_posterior(self, x, mask, q, prior, sigma, steps=200, S=1, lr=0.1, lr_final=None, optimizer="adam",
+                         betas=(0.9, 0.999), eps=1e-8, z=None, seed=1, voxel0=0, want_loss=False):
+        """Semi-amortised refinement of each voxel's heads (qbold_refine_posterior): `steps` Adam or SGD steps on the
+        voxel's E_q[nll] + closed-form KL(q || prior), S likelihood draws per step (Philox stream 7 unless z
+        [N, steps, 4 ceil(S / 4), 2] is given), sigma fixed, the rate on a cosine from lr to lr_final (None: lr / 10;
+        lr_final = lr is a constant rate).  Voxels with mask <= 0 come back unchanged.
+        Defaults: MEASUREMENTS.md section 10.
+        Returns q_out [N, 5] (raw heads, like q) and, with want_loss, loss [N, 2] = (-ELBO estimate at step 0, its
+        mean over the last ceil(steps / 10) steps)."""
+        if optimizer not in ("adam", "sgd"):
+            raise ValueError("optimizer must be 'adam' or 'sgd'")
+        steps, S = int(steps), int(S)
+        if steps < 1 or S < 1:
+            raise ValueError("refine_posterior: need steps >= 1 and S >= 1")
+        lr = float(lr)
+        lr_final = 0.1 * lr if lr_final is None else float(lr_final)
+        if not lr > 0.0 or not lr_final >= 0.0:
+            raise ValueError("refine_posterior: need lr > 0 and lr_final >= 0")
+        Sp = 4 * ((S + 3) // 4)
+        if steps * Sp // 4 >= 1 << 32:
+            raise ValueError("refine_posterior: steps * 4 ceil(S / 4) / 4 must be below 2^32 (the Philox call word)")
+        x = _f32(x, "x", self.T)
+        N = x.numel() // self.T
+        q = _f32(q, "q", 5)
+        prior = _f32(prior, "prior", 5)
+        sigma = _f32(sigma, "sigma", self.T)
+        mask = _f32(mask, "mask") if mask is not None else None
+        z = _f32(z, "z", 2) if z is not None else None
+        if z is not None and z.numel() != N * steps * Sp * 2:
+            raise ValueError("z must be [N, steps, 4 ceil(S / 4), 2]")
+        cfg = _lib.RefineCfg(0 if optimizer == "adam" else 1, lr, lr_final, float(betas[0]), float(betas[1]),
+                             float(eps))
+        q_out = torch.empty((N, 5), dtype=torch.float32, device=x.device)
+        loss = torch.empty((N, 2), dtype=torch.float32, device=x.device) if want_loss else None
+        _lib.check(self.lib.qbold_refine_posterior(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior),
+                                                   _ptr(sigma), _ptr(z), steps, S, C.byref(cfg), int(seed),
+                                                   int(voxel0), _ptr(q_out), _ptr(loss), N, _stream()),
+                   "qbold_refine_posterior")
+        return (q_out, loss) if want_loss else q_out
+
     def vi_fwd_exact(self, weights, x, mask, prior, S=1, K=70, seed=1, voxel0=0):
         """The same evaluation with the encoder on the exact-float32 layer-wise path (f32-input MFMA GEMMs,
         qbold_encoder_train_fwd) -- no f16 operand split, so no 65504 operand limit.  Slow (one launch per layer,

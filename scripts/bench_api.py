@@ -46,6 +46,24 @@ def main():
         st.backward(2, gq0, gs, None)
 
     st.forward(x, 2)
+    # per-voxel refinement at T = 11 and T = 24 (the same heads; a fixed sigma at T = 24), and the composed loop it
+    # replaces: per step qbold_elbo_bwd(S, K = 70) and qbold_adamw_step on the N x 5 heads with weight decay 0
+    ctx24 = Context(dict(params, tau_start="-0.028", tau_end="0.065", tau_step="0.004"), True, True)
+    x24 = ctx24.signal_fwd(y)
+    sg24 = torch.full((n, ctx24.T), 0.05, device="cuda")
+
+    def composed(c, xx, lsx, steps, S):
+        from qbold_vi_amd.ops import _ptr, _stream
+        qq = q.clone()
+        m1, m2 = torch.zeros_like(qq), torch.zeros_like(qq)
+        for j in range(steps):
+            _, gq, _, _ = c.elbo_bwd(xx, mask, qq, o1, lsx, S, 70, seed=1 + j)
+            c.lib.qbold_adamw_step(c.handle, _ptr(qq), _ptr(gq), _ptr(m1), _ptr(m2), 5 * n, 0.05, 0.9, 0.999, 1e-8,
+                                   0.0, j + 1, _stream())
+        return qq
+
+    def rbytes(TT):   # x, sigma, q, prior, mask in; q out
+        return 4 * (2 * TT + 10) + 4 + 20
     calls = {
         # name: (callable, algorithmic bytes per voxel)
         "signal_fwd": (lambda: ctx.signal_fwd(y), 8 + 4 * T),
@@ -68,6 +86,16 @@ def main():
         "elbo_fwd(S=64,K=64)": (lambda: ctx.elbo_fwd(x, mask, q, o1, sg, 64, 64, seed=1), 8 * T + 52),
         "log_evidence(K=1024)": (lambda: ctx.log_evidence(x, mask, q, o1, sg, 1024, seed=1), 8 * T + 52),
         "elbo_fwd(S=1024,K=1024)": (lambda: ctx.elbo_fwd(x, mask, q, o1, sg, 1024, 1024, seed=1), 8 * T + 52),
+        "refine_posterior(T=11,steps=200,S=1)": (lambda: ctx.refine_posterior(x, mask, q, o1, sg, 200, 1), rbytes(T)),
+        "refine_posterior(T=11,steps=100,S=4)": (lambda: ctx.refine_posterior(x, mask, q, o1, sg, 100, 4), rbytes(T)),
+        "refine_posterior(T=24,steps=200,S=1)": (lambda: ctx24.refine_posterior(x24, mask, q, o1, sg24, 200, 1),
+                                                 rbytes(24)),
+        "refine_posterior(T=24,steps=100,S=4)": (lambda: ctx24.refine_posterior(x24, mask, q, o1, sg24, 100, 4),
+                                                 rbytes(24)),
+        "composed_loop(T=11,steps=200,S=1,K=70)": (lambda: composed(ctx, x, ls, 200, 1), 0),
+        "composed_loop(T=11,steps=100,S=4,K=70)": (lambda: composed(ctx, x, ls, 100, 4), 0),
+        "composed_loop(T=24,steps=200,S=1,K=70)": (lambda: composed(ctx24, x24, torch.log(sg24), 200, 1), 0),
+        "composed_loop(T=24,steps=100,S=4,K=70)": (lambda: composed(ctx24, x24, torch.log(sg24), 100, 4), 0),
         "vi_fwd(S=32,K=70)": (lambda: ctx.vi_fwd(ew, x, mask, o1, 32, 70, seed=1), 4 * T + 52),
         "synth_loss_bwd": (lambda: st.synth_loss_bwd(y3, o1), 12 + 20 + 24),
         "wls_fit": (lambda: ctx.wls_fit(x), 4 * T + 12),

@@ -1,0 +1,409 @@
+"""Per-voxel posterior refinement (qbold_refine_posterior, Context.refine_posterior, FineTuner.refine): the gradient of
+one step and the whole optimiser against a float64 restatement built from the oracle's primitives
+(tests/_refine_reference.py), the Philox stream, bitwise identities, a known answer by quadrature, improvement at
+scale, argument errors and the Python surface."""
+import ctypes as C
+import gzip
+
+import numpy as np
+import pytest
+
+from _refine_reference import kl_closed_and_grad, padded_draws, refine_reference, step_grad
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+REFINE_STREAM = 7
+
+
+def dev(a):
+    return torch.as_tensor(np.ascontiguousarray(a), device="cuda")
+
+
+def _same_bits(a, b):
+    """bitwise equality (NaN included)"""
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def _p24(params):
+    return dict(params, tau_start="-0.028", tau_end="0.065", tau_step="0.004")
+
+
+def _p64(params):
+    return dict(params, tau_start="-0.015", tau_end="0.065", tau_step="0.00125")
+
+
+def _case(o32, p, n, seed, spread=0.3):
+    from oracle.oracle import init_weights, synth_inputs
+    x, _ = synth_inputs(n, p, seed=seed, oracle=o32)
+    w = init_weights(T=o32.T, U=60, L=2, seed=3)
+    w["gate_offset"] = -3.0
+    prior, q, sigma = o32.encoder_fwd(w, x)
+    q = (q + np.random.default_rng(seed).normal(size=q.shape) * spread).astype(np.float32)
+    return x, q, prior, sigma
+
+
+@pytest.fixture(scope="module")
+def ctx(params):
+    from qbold_vi_amd.ops import Context
+    c = Context(params, full_model=True, include_blood=True)
+    c.set_grad_node0(False)   # exact derivatives of the forward value, as the gradient tests take them
+    return c
+
+
+# name: (protocol, loss switches)
+GRAD_CASES = {
+    "T11": (None, {}),
+    "T24": (_p24, {}),
+    "student_t": (None, dict(student_t_df=5.0)),
+    "log_data": (None, dict(predict_log_data=True)),
+    "three_image_norm": (None, dict(multi_image_normalisation=True)),
+}
+
+
+@pytest.mark.parametrize("case", list(GRAD_CASES))
+def test_one_sgd_step_is_the_gradient(params, case):
+    """SGD, one step, explicit normals, 48 voxels (a partial wave): (q_in - q_out) / lr against central differences of
+    the float64 oracle's NLL over the same normals plus the exact closed-form KL, at
+    test_elbo_head_gradients_vs_oracle_fd's tolerance."""
+    from oracle.oracle import Oracle
+    from qbold_vi_amd.ops import Context
+    proto, sw = GRAD_CASES[case]
+    p = proto(params) if proto else params
+    c = Context(p, True, True, **sw)
+    c.set_grad_node0(False)
+    o32 = Oracle("f32", p, **sw)
+    o64 = Oracle("f64", p, node0_zero=True, **sw)
+    try:
+        n, S, lr = 48, 3, 1e-2
+        x, q, prior, sigma = _case(o32, p, n, 5)
+        z = np.zeros((n, 1, padded_draws(S), 2), np.float32)
+        z[:, 0, :S] = np.random.default_rng(8).standard_normal((n, S, 2))
+        q64 = q.astype(np.float64)
+        zs = z[:, 0, :S].astype(np.float64)
+
+        def loss(qq):
+            e = o64.elbo(x, np.ones(n), qq, prior, sigma, zs, np.zeros((n, 1, 2)))
+            return e["nll_v"] + kl_closed_and_grad(qq, prior)[0]   # the exact KL (test_refine_host)
+        q_out = c.refine_posterior(dev(x), None, dev(q), dev(prior), dev(sigma), steps=1, S=S, lr=lr,
+                                   optimizer="sgd", z=dev(z))
+        g = (q64 - q_out.cpu().numpy().astype(np.float64)) / lr
+        ref = step_grad(o64, x, q64, prior, sigma, zs)
+        h = 1e-5
+        for k in range(5):
+            d = np.zeros_like(q64)
+            d[:, k] = h
+            fd = (loss(q64 + d) - loss(q64 - d)) / (2 * h)
+            scale = np.abs(fd).max() + 1e-3
+            assert np.max(np.abs(ref[:, k] - fd)) / scale < 1e-6, (case, k)
+            err = np.max(np.abs(g[:, k] - fd)) / scale
+            print(case, k, "scale", scale, "err", err)
+            assert err < 2e-3, (case, k, err, scale)
+    finally:
+        o64.lib.qbo_set_node0_zero(0)
+
+
+@pytest.fixture(scope="module")
+def data4k(params):
+    from oracle.oracle import Oracle
+    return _case(Oracle("f32", params), params, 4096, 1)
+
+
+@pytest.mark.parametrize("opt", ["sgd", "adam"])
+def test_optimiser_matches_float64_loop(ctx, params, data4k, opt):
+    """Twenty steps, explicit normals, 4,096 voxels, against the float64 restatement of the whole loop.
+    SGD is held tight: the two runs differ by float32 and the tissue table's gradient error only, so the distance is
+    a small fraction of the distance travelled.  Adam normalises each coordinate's step to about lr whatever the
+    gradient's size, so a coordinate whose gradient is near zero (relative to float32 and table error) can step with
+    the opposite sign in one of the runs: such a coordinate may end up to about 2 lr per step apart.  Adam is held to
+    that for every coordinate and to the SGD-like bound for 99 % of them."""
+    from oracle.oracle import Oracle
+    x, q, prior, sigma = data4k
+    n, S, steps = x.shape[0], 2, 20
+    lr = 1e-4 if opt == "sgd" else 1e-2
+    Sp = padded_draws(S)
+    z = np.random.default_rng(4).standard_normal((n, steps, Sp, 2)).astype(np.float32)
+    o64 = Oracle("f64", params, node0_zero=True)
+    try:
+        ref = refine_reference(o64, x, q, prior, sigma, z, S, lr=lr, lr_final=0.0, optimizer=opt)
+    finally:
+        o64.lib.qbo_set_node0_zero(0)
+    got = ctx.refine_posterior(dev(x), None, dev(q), dev(prior), dev(sigma), steps=steps, S=S, lr=lr, lr_final=0.0,
+                               optimizer=opt, z=dev(z)).cpu().numpy().astype(np.float64)
+    assert np.all(np.isfinite(got))
+    moved = np.abs(ref - q)
+    diff = np.abs(got - ref)
+    print(opt, "moved max", moved.max(), "diff max", diff.max(), "p99", np.quantile(diff, 0.99),
+          "rel", diff.max() / moved.max())
+    if opt == "sgd":
+        assert diff.max() < 2e-3 * moved.max() + 1e-5
+    else:
+        assert diff.max() < 2.0 * lr * steps
+        assert np.quantile(diff / (moved.max(axis=0) + 1e-6), 0.99) < 2e-2
+
+
+def test_philox_stream_equals_explicit_normals(ctx, data4k):
+    x, q, prior, sigma = (dev(a[:1000]) for a in data4k)
+    n, S, steps, seed, v0 = 1000, 3, 6, 77, 123457
+    Sp = padded_draws(S)
+    a, la = ctx.refine_posterior(x, None, q, prior, sigma, steps=steps, S=S, seed=seed, voxel0=v0, want_loss=True)
+    z = ctx.normals(n, steps * Sp, stream_id=REFINE_STREAM, seed=seed, voxel0=v0).reshape(n, steps, Sp, 2)
+    b, lb = ctx.refine_posterior(x, None, q, prior, sigma, steps=steps, S=S, z=z, seed=seed, voxel0=v0,
+                                 want_loss=True)
+    assert _same_bits(a, b) and _same_bits(la, lb)
+    z6 = ctx.normals(n, steps * Sp, stream_id=6, seed=seed, voxel0=v0).reshape(n, steps, Sp, 2)
+    c6 = ctx.refine_posterior(x, None, q, prior, sigma, steps=steps, S=S, z=z6, seed=seed, voxel0=v0)
+    assert not torch.equal(c6, a)
+
+
+def test_bitwise_identities(ctx, data4k):
+    x, q, prior, sigma = (a[:3001].copy() for a in data4k)
+    n, seed, v0 = 3001, 99, 5000
+    mask = (np.random.default_rng(4).uniform(size=n) > 0.25).astype(np.float32)
+    x[mask == 0] = np.nan            # masked voxels are not read
+    q[np.flatnonzero(mask == 0)[:5]] = np.nan
+    args = [dev(x), dev(mask), dev(q), dev(prior), dev(sigma)]
+    kw = dict(steps=30, S=2, lr=0.05, lr_final=0.05, seed=seed, want_loss=True)
+    o, lo = ctx.refine_posterior(*args, voxel0=v0, **kw)
+    o2, lo2 = ctx.refine_posterior(*args, voxel0=v0, **kw)
+    assert _same_bits(o, o2) and _same_bits(lo, lo2)
+    h = 1500
+    oa, la = ctx.refine_posterior(*(a[:h] for a in args), voxel0=v0, **kw)
+    ob, lb = ctx.refine_posterior(*(a[h:] for a in args), voxel0=v0 + h, **kw)
+    assert _same_bits(o[:h], oa) and _same_bits(o[h:], ob) and _same_bits(lo[:h], la) and _same_bits(lo[h:], lb)
+    dead = torch.as_tensor(mask == 0, device="cuda")
+    assert _same_bits(o[dead], args[2][dead])
+    live = ~dead
+    assert torch.isfinite(o[live]).all() and not torch.equal(o[live], args[2][live])
+    # in place (q_out aliasing q_in) through the C ABI
+    qi = args[2].clone()
+    cfg = __import__("qbold_vi_amd._lib", fromlist=["RefineCfg"]).RefineCfg(0, 0.05, 0.05, 0.9, 0.999, 1e-8)
+    P = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+    rc = ctx.lib.qbold_refine_posterior(ctx.handle, P(args[0]), P(args[1]), P(qi), P(args[3]), P(args[4]), None, 30,
+                                        2, C.byref(cfg), seed, v0, P(qi), None, n, None)
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert _same_bits(qi, o)
+    # NaN in, NaN out
+    xn = args[0].clone()
+    xn[0] = float("nan")
+    mk = args[1].clone()
+    mk[0] = 1.0
+    on = ctx.refine_posterior(xn, mk, args[2], args[3], args[4], steps=5, S=1)
+    assert torch.isnan(on[0]).all()
+
+
+def _mvn_raw_to_chol(raw):
+    so, sd = 3 * np.tanh(raw[1]) - 1, 3 * np.tanh(raw[3]) - 1
+    return np.array([raw[0], raw[2]]), np.array([[np.exp(so), 0.0], [np.tanh(raw[4]) * np.exp(-2.0), np.exp(sd)]])
+
+
+def _quad_elbo(o64, x, sigma, prior, raw, nodes):
+    """ELBO of q = raw by 2-D Gauss-Hermite quadrature in whitened logit space (float64 oracle signal model) minus
+    the exact KL."""
+    t, w = np.polynomial.hermite.hermgauss(nodes)
+    z0, z1 = np.meshgrid(np.sqrt(2.0) * t, np.sqrt(2.0) * t, indexing="ij")
+    ww = (np.outer(w, w) / np.pi).ravel()
+    mu, L = _mvn_raw_to_chol(raw)
+    lg = mu[None] + np.stack([z0.ravel(), z1.ravel()], -1) @ L.T
+    y = np.stack([1 / (1 + np.exp(-lg[:, 0])) * 0.8 + 0.04, 1 / (1 + np.exp(-lg[:, 1])) * 0.2 + 0.001], -1)
+    m = y.shape[0]
+    nll = o64.nll(np.repeat(x[None], m, 0), np.ones(m), o64.signal_fwd(y), np.repeat(sigma[None], m, 0))
+    return -(ww * nll).sum() - o64.kl_closed(raw[None], prior[None])[0]
+
+
+def test_known_answer_by_quadrature(params):
+    """The six sigma = 0.05 voxels of test_known_answer_by_quadrature: the family's best member q* by
+    scipy.optimize on the quadrature ELBO; GPU refinement from the prior (Adam, 2,000 steps, S = 4, cosine to 0)
+    must reach q*'s ELBO within 1e-2 nats and not beat it beyond the quadrature error."""
+    scipy_opt = pytest.importorskip("scipy.optimize")
+    from oracle.oracle import Oracle, synth_inputs
+    from qbold_vi_amd.ops import Context
+    o32 = Oracle("f32", params)
+    n = 6
+    x, _ = synth_inputs(n, params, seed=21, oracle=o32)
+    sigma = np.full((n, o32.T), 0.05, np.float32)
+    prior = np.tile(np.array([-0.2, 0.3, -2.0, 0.3, 0.0], np.float32), (n, 1))
+    c = Context(params, True, True)
+    q_gpu, loss = c.refine_posterior(dev(x), None, dev(prior), dev(prior), dev(sigma), steps=2000, S=4, lr=0.1,
+                                     lr_final=0.0, seed=3, want_loss=True)
+    q_gpu = q_gpu.cpu().numpy().astype(np.float64)
+    o64 = Oracle("f64", params, node0_zero=True)
+    try:
+        for i in range(n):
+            xi, si, pi = x[i].astype(np.float64), sigma[i].astype(np.float64), prior[i].astype(np.float64)
+            f = lambda r: -_quad_elbo(o64, xi, si, pi, r, 48)   # noqa: E731
+            best = None
+            for start in (pi, q_gpu[i]):
+                res = scipy_opt.minimize(f, start, method="L-BFGS-B", options=dict(ftol=1e-14, gtol=1e-9,
+                                                                                   maxiter=5000))
+                best = res if best is None or res.fun < best.fun else best
+            e_star = -best.fun
+            e_gpu = _quad_elbo(o64, xi, si, pi, q_gpu[i], 48)
+            quad_err = abs(_quad_elbo(o64, xi, si, pi, best.x, 64) - e_star) + 1e-6
+            print(i, "q*", best.x, "elbo*", e_star, "gpu", q_gpu[i], "elbo", e_gpu, "quad err", quad_err,
+                  "loss", loss[i].tolist())
+            assert e_gpu > e_star - 1e-2, (i, e_gpu, e_star)
+            assert e_gpu < e_star + quad_err, (i, e_gpu, e_star, quad_err)
+    finally:
+        o64.lib.qbo_set_node0_zero(0)
+    # the refined q is closer to the posterior: the importance-weighted gap log p^ - ELBO shrinks
+    _, o0, _ = c.log_evidence(dev(x), None, dev(prior), dev(prior), dev(sigma), 4096, seed=9)
+    _, o1, _ = c.log_evidence(dev(x), None, dev(q_gpu.astype(np.float32)), dev(prior), dev(sigma), 4096, seed=9)
+    gap0 = (o0[:, 0] - o0[:, 1]).cpu().numpy()
+    gap1 = (o1[:, 0] - o1[:, 1]).cpu().numpy()
+    print("gap start", gap0, "gap refined", gap1)
+    assert np.all(gap1 <= gap0)
+
+
+def test_improvement_at_scale(ctx, params):
+    """1 M synthetic voxels, heads from an untrained encoder (perturbed), default settings: per voxel the -ELBO at
+    S = 32, K = 70 (a seed the refinement does not use; the same draws before and after) drops for >= 95 % of the
+    masked voxels, the mean drops, no NaN."""
+    from qbold_vi_amd import EncoderTrainer
+    from qbold_vi_amd.signals import create_synthetic_dataset
+    x, _ = create_synthetic_dataset(params, True, True, 0.0, sample_size=1000, seed=3)
+    n = x.shape[0]
+    assert n == 1_000_000
+    tr = EncoderTrainer(system_params=params, no_units=60, no_intermediate_layers=2, initial_im_sigma=0.05,
+                        activation_type='relu', multi_image_normalisation=False, channelwise_gating=True,
+                        use_population_prior=False, use_mvg=True, predict_log_data=False)
+    model, _ = tr.create_encoder(gate_offset=-3.0, resid_init_std=0.05, no_ip_images=11)
+    prior, q, sg = model.predict(x, want=("out1", "out2", "sigma"))
+    g = torch.Generator(device="cuda").manual_seed(5)
+    q = (q + 0.5 * torch.randn(q.shape, device="cuda", generator=g)).contiguous()
+    mask = (torch.rand(n, device="cuda", generator=g) > 0.1).float()
+    q_ref = ctx.refine_posterior(x, mask, q, prior, sg)
+    assert not torch.isnan(q_ref).any()
+    _, before = ctx.elbo_fwd(x, mask, q, prior, sg, 32, 70, seed=424242)
+    _, after = ctx.elbo_fwd(x, mask, q_ref, prior, sg, 32, 70, seed=424242)
+    live = mask > 0
+    b = before.sum(1)[live]
+    a = after.sum(1)[live]
+    assert torch.isfinite(a).all()
+    frac = (a < b).double().mean().item()
+    print("fraction improved", frac, "mean -ELBO", b.mean().item(), "->", a.mean().item())
+    assert frac >= 0.95
+    assert a.mean() < b.mean()
+
+
+def test_bad_arguments(ctx, params, data4k):
+    from qbold_vi_amd import _lib
+    from qbold_vi_amd.ops import Context
+    x, q, prior, sigma = (dev(a[:64]) for a in data4k)
+    out = torch.empty((64, 5), device="cuda")
+    P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+
+    def call(c, steps=5, S=1, lr=0.05, o=out, opt=0, qq=q):
+        cfg = _lib.RefineCfg(opt, lr, lr, 0.9, 0.999, 1e-8)
+        return c.lib.qbold_refine_posterior(c.handle, P(x), None, P(qq), P(prior), P(sigma), None, steps, S,
+                                            C.byref(cfg), 1, 0, P(o), None, 64, None)
+    assert call(ctx, steps=0) == -1 and call(ctx, S=0) == -1 and call(ctx, lr=0.0) == -1 and call(ctx, lr=-1.0) == -1
+    assert call(ctx, o=None) == -1 and call(ctx, qq=None) == -1 and call(ctx, opt=2) == -1
+    # steps * Sp / 4 = (2^31 - 1) * 3 >= 2^32: the Philox call word would wrap
+    assert call(ctx, steps=(1 << 31) - 1, S=9) == -1
+    assert call(ctx) == _lib.QBOLD_OK
+    torch.cuda.synchronize()
+    with pytest.raises(ValueError, match="z must be"):
+        ctx.refine_posterior(x, None, q, prior, sigma, steps=5, S=1, z=torch.zeros((64, 5, 3, 2), device="cuda"))
+    # configurations without a kernel: 64 taus, the literal tissue integral
+    c64 = Context(_p64(params), True, True)
+    assert c64.T == 64
+    assert call(c64) == -3
+    cl = Context(params, True, True)
+    cl.set_tissue_mode("literal")
+    assert call(cl) == -3
+
+
+@pytest.fixture(scope="module")
+def trainer(params):
+    from qbold_vi_amd import EncoderTrainer
+    return EncoderTrainer(system_params=params, no_units=60, use_layer_norm=False, dropout_rate=0.0,
+                          no_intermediate_layers=2, initial_im_sigma=0.05, activation_type='relu',
+                          multi_image_normalisation=False, channelwise_gating=True, infer_inv_gamma=False,
+                          use_population_prior=False, use_mvg=True, predict_log_data=False)
+
+
+def _fine_tuner(tr, params, model=None):
+    from qbold_vi_amd import SignalGenerationLayer
+    if model is None:
+        model, _ = tr.create_encoder(gate_offset=-3.0, resid_init_std=0.05, no_ip_images=11)
+    return model, tr.build_fine_tuner(model, SignalGenerationLayer(dict(params, simulate_noise='False'), True, True))
+
+
+def test_fine_tuner_refine_voxel_batch_and_crops(trainer, params):
+    from oracle.oracle import Oracle, synth_inputs
+    o32 = Oracle("f32", params)
+    model, ft = _fine_tuner(trainer, params)
+    for lead, seed in (((1000, 1, 1, 1), 3), ((2, 19, 13, 4), 8)):
+        nv = int(np.prod(lead))
+        x, _ = synth_inputs(nv, params, seed=seed, oracle=o32)
+        x5 = dev(x).reshape(lead + (11,))
+        m5 = dev((np.random.default_rng(seed).uniform(size=nv) > 0.3).astype(np.float32)).reshape(lead + (1,))
+        p5 = model(x5)[0]
+        got = ft.refine(x5, m5, p5, steps=50, no_samples=2, seed=4, voxel0=7)
+        assert got["q"].shape == lead + (5,) and got["loss"].shape == lead + (2,)
+        _, q5, sg5 = model.predict(x5, want=("out2", "sigma"))
+        want, loss = trainer.context.refine_posterior(x5.reshape(-1, 11), m5.reshape(-1), q5.reshape(-1, 5),
+                                                      p5.reshape(-1, 5), sg5.reshape(-1, 11), steps=50, S=2,
+                                                      lr=0.1, lr_final=0.01, seed=4, voxel0=7, want_loss=True)
+        assert _same_bits(got["q"].reshape(-1, 5), want) and _same_bits(got["loss"].reshape(-1, 2), loss)
+        live = m5.reshape(-1) > 0
+        assert (loss[live, 1] < loss[live, 0]).double().mean().item() > 0.9
+        # q=None scores the encoder's heads; q= scores the given ones
+        e0 = ft.elbo(x5, m5, p5, no_samples=4, seed=2)
+        e1 = ft.elbo(x5, m5, p5, no_samples=4, seed=2, q=q5)
+        if x5.shape[1] > 1:   # crops: both through the spatial encoder and the ELBO kernel
+            assert _same_bits(e0["nll_kl"], e1["nll_kl"])
+        else:                 # voxel batch: the fused encoder + ELBO launch against the ELBO kernel on its heads
+            assert torch.allclose(e0["sums"], e1["sums"], rtol=1e-3)
+        e2 = ft.elbo(x5, m5, p5, no_samples=4, seed=2, q=got["q"])
+        assert e2["elbo"] < e0["elbo"]
+        l0 = ft.log_evidence(x5, m5, p5, no_samples=16, seed=2)
+        l1 = ft.log_evidence(x5, m5, p5, no_samples=16, seed=2, q=q5)
+        assert _same_bits(l0["log_evidence"], l1["log_evidence"])
+
+
+def test_fine_tuner_refine_refuses_the_diagonal_family(params):
+    from qbold_vi_amd import EncoderTrainer
+    tr = EncoderTrainer(system_params=params, no_units=30, use_mvg=False, use_population_prior=False,
+                        activation_type='relu', predict_log_data=False)
+    model, ft = _fine_tuner(tr, params)
+    x5 = torch.ones((4, 1, 1, 1, 11), device="cuda")
+    with pytest.raises(NotImplementedError, match="diagonal family"):
+        ft.refine(x5, torch.ones((4, 1, 1, 1, 1), device="cuda"), torch.zeros((4, 1, 1, 1, 4), device="cuda"))
+
+
+def test_save_predictions_writes_the_refined_maps(trainer, params, tmp_path):
+    import os
+    from oracle.oracle import Oracle, synth_inputs
+    from qbold_vi_amd import nifti
+    model, ft = _fine_tuner(trainer, params)
+    B, X, Y, Z = 2, 6, 5, 4
+    x, _ = synth_inputs(B * X * Y * Z, params, seed=12, oracle=Oracle("f32", params))
+    mask = (np.random.default_rng(1).uniform(size=(B * X * Y * Z, 1)) > 0.2).astype(np.float32)
+    data = dev(np.concatenate([x, mask], -1)).reshape(B, X, Y, Z, 12)
+    priors = model(data[..., :-1])[0]
+    d0, d1 = tmp_path / "plain", tmp_path / "refined"
+    os.makedirs(d0)
+    os.makedirs(d1)
+    assert trainer.save_predictions(model, data, str(d0 / "sub"), fine_tuner_model=ft, priors=priors) is None
+    _, ft1 = _fine_tuner(trainer, params, model)   # a fresh fine tuner: its sampling layer counts its calls
+    maps = trainer.save_predictions(model, data, str(d1 / "sub"), fine_tuner_model=ft1, priors=priors,
+                                    refine_steps=200)
+    extra = {f"sub_{k}.nii.gz" for k in ("oef_refined", "dbv_refined", "r2p_refined", "amortgap")}
+    plain = set(os.listdir(d0))
+    assert set(os.listdir(d1)) == plain | extra and not (plain & extra)
+    for f in plain:   # the earlier maps are unchanged, byte for byte (gzip stamps the time, so compare the content)
+        with gzip.open(d0 / f, "rb") as a, gzip.open(d1 / f, "rb") as b:
+            assert a.read() == b.read(), f
+    live = mask.reshape(B, X, Y, Z) > 0
+    for k in ("oef_refined", "dbv_refined", "r2p_refined", "amortgap"):
+        v = maps[k].cpu().numpy()
+        assert v.shape == (B, X, Y, Z, 1) and np.all(np.isfinite(v))
+        img = nifti.load(str(d1 / f"sub_{k}.nii.gz"))[0]
+        np.testing.assert_array_equal(img, np.concatenate(np.split(v, B, axis=0), axis=-1)[0])
+    gap = maps["amortgap"].cpu().numpy()[..., 0]
+    assert np.all(gap[~live] == 0.0)
+    print("amortisation gap over the mask", gap[live].mean())
+    assert gap[live].mean() >= 0.0
