@@ -410,6 +410,49 @@ int qbold_refine_posterior(const qbold_ctx* ctx, const float* x, const float* ma
                            const qbold_refine_cfg* cfg, uint64_t seed, int64_t voxel0,
                            float* q_out, float* loss, int64_t N, void* stream);
 
+/* Exact per-voxel posteriors of the fine-tuning model by quadrature on the logit plane (this package's addition; the
+ * reference has no counterpart).  With sigma fixed the latent space is u = (a, b), the logits of (OEF, DBV), and
+ *   J(u) = -nll(x | OEF(clip a), DBV(clip b); sigma) + log N(u; mu_p, Sigma_p)
+ * is the log-joint (nll: qbold_elbo_fwd's per-draw NLL with every likelihood switch; clip at +-13.8155, the logit
+ * clip of model.py:393-396; N: the prior's logit-space Gaussian, make_mvn of prior[5]); the sigmoid Jacobians cancel,
+ * so its integral over u is the log p(x) that qbold_log_evidence_fwd converges to.
+ *   1. Start box B0: a in mu_a +- span sd_a, b in mu_b +- span sd_b (Sigma_p's marginal sds); with q, the bounding box
+ *      of that box and q's; intersected with [-clip, clip]^2.
+ *   2. locate passes k = 1 .. locate: coarse x coarse nodes at linspace points over B_{k-1} (endpoints included);
+ *      M = max J; keep the rows whose maximum J exceeds M - cut, and the columns likewise; B_k = the range of the kept
+ *      rows and columns widened by one node step on each side, intersected with B_{k-1}.
+ *   3. fine pass: fine x fine linspace nodes over B_locate, steps h_a, h_b, equal weights w_ij = exp(J_ij - M_f).
+ *   4. out [N][QBOLD_GRID_OUT]:
+ *      0 log_p = M_f + log sum w + log(h_a h_b)
+ *      1 elbo_q = E_q[-nll] - KL(q || prior): E_q by the gh x gh product Gauss-Hermite rule in q's whitened
+ *        coordinates (u = mu_q + L_q sqrt(2) t), the KL in closed form (qbold_refine_posterior's); NaN when q is NULL
+ *        or gh = 0
+ *      2-4 posterior means of OEF, DBV, R2' = dw_coef OEF DBV;  5-7 their posterior sds;  8 corr(OEF, DBV)
+ *      9-10 OEF quantiles at level_lo, level_hi; 11-12 DBV quantiles: of the logit marginals (row sums, column sums),
+ *        each node's mass spread uniformly over its cell [u_i - h/2, u_i + h/2] (the CDF linear within a cell),
+ *        mapped through forward_transform (monotone)
+ *      13-14 OEF, DBV at the fine grid's argmax node (a tie goes to the lowest row-major index)
+ *      15 edge_mass = the mass on the fine grid's outer ring / sum w (large: the box truncated the posterior)
+ *      16 quad_err = |log Z_h - log Z_2h|, Z_2h = 4 h_a h_b sum over even i, even j of w_ij (large: under-resolved)
+ *   box [N][4] or NULL: (a_lo, a_hi, b_lo, b_hi) of the fine pass.
+ *   Voxels with mask <= 0 (or NaN) are not evaluated: NaN rows, nothing in the sums; mask NULL evaluates every voxel.
+ *   sums: DEVICE double[3] = (sum_{m>0} m (-log_p), sum_{m>0} m (-elbo_q) (0 without q), sum_{m>0} m), overwritten
+ *     (qbold_log_evidence_fwd's layout).  No random stream, no atomics: a voxel's outputs are the same bits in any
+ *     batch at any position.
+ *   workspace: qbold_elbo_workspace_bytes() bytes; x, mask, prior, sigma, q (heads [N][5]), stream as qbold_elbo_fwd.
+ * Defaults: coarse 32, fine 64, locate 2, gh 16, span 6, cut 40, levels 0.025 / 0.975.  Configurations
+ * qbold_log_evidence_fwd accepts; QBOLD_ERR_UNSUPPORTED otherwise.  QBOLD_ERR_INVALID for coarse not a multiple of 8
+ * in [16, 128], fine not a multiple of 8 in [16, 256], locate outside [1, 4], gh not 0 or in [2, 32], span <= 0, cut
+ * outside [10, 80], levels not 0 < level_lo < level_hi < 1, or a NULL required buffer. */
+typedef struct {
+    int coarse, fine, locate, gh;
+    float span, cut, level_lo, level_hi;
+} qbold_grid_cfg;
+#define QBOLD_GRID_OUT 17
+int qbold_posterior_grid(const qbold_ctx* ctx, const float* x, const float* mask, const float* prior,
+                         const float* sigma, const float* q, const qbold_grid_cfg* cfg, float* out, float* box,
+                         double* sums, void* workspace, int64_t N, void* stream);
+
 /* ---- gradients (training) ------------------------------------------------------------------- */
 /* Adjoint of qbold_elbo_fwd with respect to the encoder's head outputs: what TensorFlow autodiff
  * yields through build_fine_tuner's sampling + fine_tune_loss_fn + kl_loss (model.py:239-286,

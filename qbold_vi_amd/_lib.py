@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("QBOLD_LIB") or os.path.join(_HERE, "libqbold_hip.so")
 QBOLD_OK = 0
 QBOLD_TISSUE_TABLE = 0
 QBOLD_TISSUE_LITERAL = 1
+QBOLD_GRID_OUT = 17   # columns of qbold_posterior_grid's out
 
 
 class QboldError(RuntimeError):
@@ -44,6 +45,12 @@ class RefineCfg(C.Structure):
     """qbold_refine_cfg: optimizer 0 = Adam, 1 = SGD; the learning rate follows a cosine from lr to lr_final."""
     _fields_ = [("optimizer", C.c_int32), ("lr", C.c_float), ("lr_final", C.c_float), ("beta1", C.c_float),
                 ("beta2", C.c_float), ("eps", C.c_float)]
+
+
+class GridCfg(C.Structure):
+    """qbold_grid_cfg: grid sides, locate passes, Gauss-Hermite order, start-box span, keep cut, quantile levels."""
+    _fields_ = [("coarse", C.c_int32), ("fine", C.c_int32), ("locate", C.c_int32), ("gh", C.c_int32),
+                ("span", C.c_float), ("cut", C.c_float), ("level_lo", C.c_float), ("level_hi", C.c_float)]
 
 
 class Geometry(C.Structure):
@@ -122,6 +129,7 @@ SIGNATURES = {
     "qbold_adamw_step": (C.c_int, [_P, _P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double,
                                    C.c_double, C.c_double, _I64, _P]),
     "qbold_log_evidence_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
+    "qbold_posterior_grid": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GridCfg), _P, _P, _P, _P, _I64, _P]),
     "qbold_refine_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(RefineCfg), _U64,
                                          _I64, _P, _P, _I64, _P]),
     "qbold_vi_fwd": (C.c_int, [_P, C.POINTER(EncoderShape), _P, _P, _P, _P, C.c_int, C.c_int,

@@ -318,6 +318,36 @@ class FineTuner:
         lead = data.shape[:-1]
         return dict(q=q_out.reshape(lead + (5,)), loss=loss.reshape(lead + (2,)))
 
+    def posterior_grid(self, data, mask, prior, q=None, **grid_kw):
+        """Exact per-voxel posteriors by quadrature on the logit plane (Context.posterior_grid; grid_kw: coarse, fine,
+        locate, gh, span, cut, levels, want_box), for the heads q [..., 5] (None: the encoder heads of
+        encoder_model.predict, as log_evidence() takes them) and the sigma that goes with them.  Shaped like the
+        data's spatial dims:
+          log_evidence, elbo (exact ELBO of q), gap = log_evidence - elbo (the exact KL(q || p(z | x)))
+          oef, dbv, r2p and oef_sd, dbv_sd, r2p_sd (posterior means and sds), corr (OEF-DBV posterior correlation)
+          oef_ci, dbv_ci [..., 2] (credible intervals at `levels`), map [..., 2] (OEF, DBV at the grid's maximum)
+          edge_mass, quad_err (large: the grid truncated / under-resolved the posterior), box [..., 4] or None
+        and the masked sums (distributed.allreduce_sums reduces them across shards) with mean_log_evidence,
+        mean_elbo and gap (mean_log_evidence - mean_elbo).  Voxels outside the mask are NaN."""
+        from .distributed import log_evidence_from_sums
+        tr = self._trainer
+        self._check_mvn_family("posterior_grid")
+        T = data.shape[-1]
+        x = _flat(data, T)
+        m = None if mask is None else mask.reshape(-1)
+        p5 = _flat(prior, prior.shape[-1]).contiguous()
+        q, sg = self._heads_and_sigma(data, q)
+        sums, out, box = tr._ctx.posterior_grid(x, m, p5, sg, q=q, **grid_kw)
+        lead = data.shape[:-1]
+        col = lambda i: out[:, i].reshape(lead)   # noqa: E731
+        lp, el, gap = log_evidence_from_sums(sums)
+        return dict(log_evidence=col(0), elbo=col(1), gap=col(0) - col(1), oef=col(2), dbv=col(3), r2p=col(4),
+                    oef_sd=col(5), dbv_sd=col(6), r2p_sd=col(7), corr=col(8),
+                    oef_ci=out[:, 9:11].reshape(lead + (2,)), dbv_ci=out[:, 11:13].reshape(lead + (2,)),
+                    map=out[:, 13:15].reshape(lead + (2,)), edge_mass=col(15), quad_err=col(16),
+                    box=None if box is None else box.reshape(lead + (4,)), sums=sums, mean_log_evidence=lp,
+                    mean_elbo=el, mean_gap=gap)
+
 
 class EncoderTrainer:
     def __init__(self,
@@ -665,7 +695,8 @@ class EncoderTrainer:
         return tuple(out)
 
     def save_predictions(self, model, data, filename, transform_directory=None, use_first_op=True,
-                         fine_tuner_model=None, priors=None, iw_samples=None, refine_steps=None):
+                         fine_tuner_model=None, priors=None, iw_samples=None, refine_steps=None,
+                         posterior_grid=None):
         """model.py:772-887: write `<filename>_{oef,dbv,r2p,logstds}.nii.gz` (posterior means of
         OEF / DBV / R2' over 200 draws and their variances) and, with a fine tuner,
         `_likelihood` (per-voxel NLL averaged over 100 stochastic passes), `_kl` (100-draw KL to
@@ -677,6 +708,11 @@ class EncoderTrainer:
         (FineTuner.refine) and also write `_oef_refined`, `_dbv_refined`, `_r2p_refined` (calculate_means of the
         refined heads) and `_amortgap` (per-voxel ELBO of the refined heads minus that of the encoder's, both from
         FineTuner.elbo(q=...) on the same draws; zero outside the mask); these maps join the returned dict.
+        posterior_grid = True or a dict of grid keywords (with a fine tuner; this package's addition): the exact
+        posterior by quadrature of the encoder's heads (FineTuner.posterior_grid) as `_oef_exact`, `_dbv_exact`,
+        `_r2p_exact`, `_oef_exact_sd`, `_dbv_exact_sd`, `_oef_ci_lo`, `_oef_ci_hi`, `_dbv_ci_lo`, `_dbv_ci_hi`,
+        `_logevidence_exact`, `_vigap_exact` (log p(x) - ELBO of the encoder's heads) and `_gridedge` (edge_mass),
+        zero outside the mask; these maps join the returned dict.
         data [subj, X, Y, Z, T+1] with the mask last; each map is stored as [X, Y, Z, subj*C].
         `transform_directory/example.nii.gz`, when present, donates its header (:794-797); the
         FSL `applywarp`/`fslmerge` MNI step (:850-879) is preprocessing outside this package and
@@ -757,6 +793,23 @@ class EncoderTrainer:
             for k, v in ref_maps.items():
                 save_im_data(v, filename + '_' + k)
             iw_maps = dict(iw_maps or {}, **ref_maps)
+
+        if fine_tuner_model and posterior_grid:
+            kw = dict(posterior_grid) if isinstance(posterior_grid, dict) else {}
+            pg = fine_tuner_model.posterior_grid(data[..., :-1], mask,
+                                                 torch.as_tensor(priors, device=data.device)[..., :self._nq], **kw)
+            live = mask[..., 0] > 0
+            zero = torch.zeros_like(pg["oef"])
+            grid_maps = {k: torch.where(live, v, zero)[..., None] for k, v in
+                         (("oef_exact", pg["oef"]), ("dbv_exact", pg["dbv"]), ("r2p_exact", pg["r2p"]),
+                          ("oef_exact_sd", pg["oef_sd"]), ("dbv_exact_sd", pg["dbv_sd"]),
+                          ("oef_ci_lo", pg["oef_ci"][..., 0]), ("oef_ci_hi", pg["oef_ci"][..., 1]),
+                          ("dbv_ci_lo", pg["dbv_ci"][..., 0]), ("dbv_ci_hi", pg["dbv_ci"][..., 1]),
+                          ("logevidence_exact", pg["log_evidence"]), ("vigap_exact", pg["gap"]),
+                          ("gridedge", pg["edge_mass"]))}
+            for k, v in grid_maps.items():
+                save_im_data(v, filename + '_' + k)
+            iw_maps = dict(iw_maps or {}, **grid_maps)
 
         save_im_data(means[..., 0:1], filename + '_oef')
         save_im_data(means[..., 1:2], filename + '_dbv')

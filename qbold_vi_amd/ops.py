@@ -4,6 +4,7 @@ PyTorch owns the memory and the stream; every number is produced by libqbold_hip
 be float32 CUDA (HIP) tensors -- CPU tensors are rejected, there is no host fallback.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -502,6 +503,53 @@ class Context:
                                                    int(voxel0), _ptr(q_out), _ptr(loss), N, _stream()),
                    "qbold_refine_posterior")
         return (q_out, loss) if want_loss else q_out
+
+    GRID_COLUMNS = ("log_p", "elbo_q", "oef", "dbv", "r2p", "oef_sd", "dbv_sd", "r2p_sd", "corr", "oef_lo", "oef_hi",
+                    "dbv_lo", "dbv_hi", "map_oef", "map_dbv", "edge_mass", "quad_err")
+
+    def posterior_grid(self, x, mask, prior, sigma, q=None, coarse=32, fine=64, locate=2, gh=16, span=6.0, cut=40.0,
+                       levels=(0.025, 0.975), want_box=False):
+        """Exact per-voxel posteriors by quadrature on the logit plane (qbold_posterior_grid): `locate` coarse
+        x coarse passes shrink the start box (prior, and q's, +- span sds) to where the log-joint is within `cut` of
+        its maximum, then one fine x fine pass integrates.  q (heads [N, 5]) adds the exact ELBO(q) by a gh x gh
+        Gauss-Hermite rule; None (or gh = 0) leaves that column NaN.  Voxels with mask <= 0 come back NaN.
+        Returns (sums double[3] device tensor = (sum [m>0] m (-log_p), sum [m>0] m (-elbo_q), sum [m>0] m),
+        out [N, 17] with the columns of GRID_COLUMNS, box [N, 4] = the fine pass's (a_lo, a_hi, b_lo, b_hi) or None)."""
+        coarse, fine, locate, gh = int(coarse), int(fine), int(locate), int(gh)
+        span, cut = float(span), float(cut)
+        lo, hi = (float(v) for v in levels)
+        if coarse % 8 or not 16 <= coarse <= 128:
+            raise ValueError("posterior_grid: coarse must be a multiple of 8 in [16, 128]")
+        if fine % 8 or not 16 <= fine <= 256:
+            raise ValueError("posterior_grid: fine must be a multiple of 8 in [16, 256]")
+        if not 1 <= locate <= 4:
+            raise ValueError("posterior_grid: locate must be in [1, 4]")
+        if gh != 0 and not 2 <= gh <= 32:
+            raise ValueError("posterior_grid: gh must be 0 or in [2, 32]")
+        if not 0.0 < span < math.inf:
+            raise ValueError("posterior_grid: need span > 0")
+        if not 10.0 <= cut <= 80.0:
+            raise ValueError("posterior_grid: cut must be in [10, 80]")
+        if not 0.0 < lo < hi < 1.0:
+            raise ValueError("posterior_grid: need 0 < levels[0] < levels[1] < 1")
+        for name, t in (("x", x), ("prior", prior), ("sigma", sigma), ("mask", mask), ("q", q)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+                raise ValueError(f"posterior_grid: {name} must be a cuda (ROCm) tensor; there is no CPU fallback")
+        x = _f32(x, "x", self.T)
+        N = x.numel() // self.T
+        prior = _f32(prior, "prior", 5)
+        sigma = _f32(sigma, "sigma", self.T)
+        mask = _f32(mask, "mask") if mask is not None else None
+        q = _f32(q, "q", 5) if q is not None else None
+        cfg = _lib.GridCfg(coarse, fine, locate, gh, span, cut, lo, hi)
+        sums = torch.empty(3, dtype=torch.float64, device=x.device)
+        out = torch.empty((N, _lib.QBOLD_GRID_OUT), dtype=torch.float32, device=x.device)
+        box = torch.empty((N, 4), dtype=torch.float32, device=x.device) if want_box else None
+        _lib.check(self.lib.qbold_posterior_grid(self.handle, _ptr(x), _ptr(mask), _ptr(prior), _ptr(sigma), _ptr(q),
+                                                 C.byref(cfg), _ptr(out), _ptr(box), _ptr(sums),
+                                                 _ptr(self._workspace()), N, _stream()),
+                   "qbold_posterior_grid")
+        return sums, out, box
 
     def vi_fwd_exact(self, weights, x, mask, prior, S=1, K=70, seed=1, voxel0=0):
         """The same evaluation with the encoder on the exact-float32 layer-wise path (f32-input MFMA GEMMs,
