@@ -312,8 +312,8 @@ int qbold_kl_diag(const qbold_ctx* ctx, const float* q, const float* prior, cons
 
 /* The counter-based normal stream the fused kernels consume: z [N][n][2] for global voxels
  * voxel0 .. voxel0+N-1; stream_id 0 = likelihood draws, 1 = KL draws, 2 = moments, 3 = noise, 6 = the importance
- * draws of qbold_log_evidence_fwd, 7 = the refinement draws of qbold_refine_posterior (4 is qbold_kl_mog's, 5 the
- * dropout masks').
+ * draws of qbold_log_evidence_fwd, 7 = the refinement draws of qbold_refine_posterior, 8 = the predictive draws of
+ * qbold_posterior_predictive (4 is qbold_kl_mog's, 5 the dropout masks').
  * Replaces tf.random.normal at model.py:25 with a reproducible, sharding-invariant generator
  * (Random123 Philox4x32-7, four draws per call: draw i = word i & 3 of call i >> 2 keyed (voxel, call, stream_id; seed);
  * Box-Muller on the word's low sixteen bits (radius, u1 = (lo + 0.5) 2^-16, so |z| <= 4.8549) and top 23 bits (angle,
@@ -452,6 +452,40 @@ typedef struct {
 int qbold_posterior_grid(const qbold_ctx* ctx, const float* x, const float* mask, const float* prior,
                          const float* sigma, const float* q, const qbold_grid_cfg* cfg, float* out, float* box,
                          double* sums, void* workspace, int64_t N, void* stream);
+
+/* Posterior predictive checks of the fine-tuning model per voxel (this package's addition; the reference has no
+ * counterpart): Gelman, Meng & Stern 1996 for the p-value, Watanabe 2010 / Vehtari, Gelman & Gabry 2017 for lppd and
+ * WAIC.  theta_l, l = 0 .. L-1: the reparameterised draws of q (heads [N][5], the use_mvg = True family), from explicit
+ * normals z [N][L][2] or, z NULL, draw l of qbold_normals(seed, 8, voxel0 + i, L) for voxel i (Philox stream 8).
+ * Everything lives in the likelihood's own space, the one qbold_elbo_fwd scores: y_t the data normalised by the
+ * spin-echo image (the mean of three with multi-image normalisation) + 1e-3, logged when predict_log; yh_{l,t} draw l's
+ * prediction normalised the same way; r_{l,t} = (y_t - yh_{l,t}) / sigma_t; log p(y_t | theta_l) the per-tau term of
+ * the NLL (Gaussian or Student-t).  No prior is involved.
+ *   out [N][QBOLD_PPC_OUT]:
+ *     0 ppp       = mean_l Q_{chi2_T}(D_l), D_l = sum_t r_{l,t}^2: the posterior predictive p-value of the chi2
+ *                   discrepancy, Rao-Blackwellised (under the Gaussian likelihood D(y_rep, theta) ~ chi2_T exactly, so
+ *                   no replicate noise is drawn); Q by its finite series.  NaN under Student-t.
+ *     1 dbar      = mean_l D_l
+ *     2 lppd      = sum_t log mean_l p(y_t | theta_l)   (streaming log-sum-exp per tau, relative to a running max)
+ *     3 p_waic    = sum_t var_l log p(y_t | theta_l)    (denominator L - 1, from sums shifted by draw 0's value)
+ *     4 elpd_waic = lppd - p_waic
+ *     5 max_abs_z = max_t |z_t|
+ *   curves [N][T][3] or NULL: (mu_t, sd_t, z_t) with mu_t = mean_l yh_{l,t}, sd_t = sqrt(var_l yh_{l,t} + v sigma_t^2)
+ *     (v = 1 for the Gaussian, df / (df - 2) for Student-t, +inf for df <= 2), z_t = (y_t - mu_t) / sd_t: the fitted
+ *     curve with its predictive band.
+ *   Rows with mask <= 0 (or NaN) are NaN in out and curves and add nothing to the sums; mask NULL evaluates every voxel.
+ *   sums: DEVICE double[4] = (sum m elpd_waic, sum m p_waic, sum m ppp, sum m) over the voxels with m > 0, overwritten
+ *     (fixed-order reductions, no atomics: a voxel's outputs are the same bits at any batch position).
+ *   workspace: qbold_elbo_workspace_bytes() bytes; x, mask, sigma (exponentiated), stream as qbold_elbo_fwd.
+ * The observed r at the spin-echo image is ~0 by construction (the data are normalised by it), while chi2_T counts a
+ * degree of freedom there: ppp is skewed upward on well-specified voxels and flags fewer, never more (at T = 11,
+ * sigma = 0.01, q at the true parameters: 3.5 % below 0.05, 0.64 % below 0.01; MEASUREMENTS.md section 12).
+ * Configurations qbold_log_evidence_fwd accepts; QBOLD_ERR_UNSUPPORTED otherwise.  QBOLD_ERR_INVALID for L < 2,
+ * L > 2^30 or a NULL out / sums / workspace. */
+#define QBOLD_PPC_OUT 6
+int qbold_posterior_predictive(const qbold_ctx* ctx, const float* x, const float* mask, const float* q,
+                               const float* sigma, const float* z, int L, uint64_t seed, int64_t voxel0,
+                               float* out, float* curves, double* sums, void* workspace, int64_t N, void* stream);
 
 /* ---- gradients (training) ------------------------------------------------------------------- */
 /* Adjoint of qbold_elbo_fwd with respect to the encoder's head outputs: what TensorFlow autodiff

@@ -15,6 +15,7 @@ QBOLD_OK = 0
 QBOLD_TISSUE_TABLE = 0
 QBOLD_TISSUE_LITERAL = 1
 QBOLD_GRID_OUT = 17   # columns of qbold_posterior_grid's out
+QBOLD_PPC_OUT = 6     # columns of qbold_posterior_predictive's out
 
 
 class QboldError(RuntimeError):
@@ -130,6 +131,7 @@ SIGNATURES = {
                                    C.c_double, C.c_double, _I64, _P]),
     "qbold_log_evidence_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
     "qbold_posterior_grid": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GridCfg), _P, _P, _P, _P, _I64, _P]),
+    "qbold_posterior_predictive": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
     "qbold_refine_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(RefineCfg), _U64,
                                          _I64, _P, _P, _I64, _P]),
     "qbold_vi_fwd": (C.c_int, [_P, C.POINTER(EncoderShape), _P, _P, _P, _P, C.c_int, C.c_int,

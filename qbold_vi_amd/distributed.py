@@ -119,3 +119,10 @@ def log_evidence_from_sums(sums):
     lp = -sums[0] / sums[2]
     el = -sums[1] / sums[2]
     return lp, el, lp - el
+
+
+def ppc_from_sums(sums):
+    """(mean elpd_waic, mean p_waic, mean ppp) over the masked voxels from the reduced sums of
+    qbold_posterior_predictive (double[4]: sum m elpd_waic, sum m p_waic, sum m ppp, sum m); they add across shards
+    (allreduce_)."""
+    return sums[0] / sums[3], sums[1] / sums[3], sums[2] / sums[3]

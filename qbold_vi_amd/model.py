@@ -348,6 +348,35 @@ class FineTuner:
                     box=None if box is None else box.reshape(lead + (4,)), sums=sums, mean_log_evidence=lp,
                     mean_elbo=el, mean_gap=gap)
 
+    def posterior_predictive(self, data, mask, q=None, no_samples=256, seed=1, voxel0=0, want_curves=False):
+        """Posterior predictive checks of `no_samples` = L draws per voxel (Context.posterior_predictive) for the heads q
+        [..., 5] (None: the encoder heads of encoder_model.predict; refine()'s output, say) and the sigma that goes with
+        them, in the likelihood's own space.  Shaped like the data's spatial dims:
+          ppp        posterior predictive p-value of the chi2 discrepancy (small: the model misfits the voxel; NaN under
+                     Student-t)
+          dbar       mean chi2 discrepancy;  lppd, p_waic, elpd_waic = lppd - p_waic (pointwise predictive accuracy)
+          max_abs_z  the largest standardised residual over the taus
+          pred_mean, pred_sd, std_resid [..., T] (want_curves): the fitted curve, its predictive sd, (y - mean) / sd
+        and the masked sums with mean_elpd_waic, mean_p_waic, mean_ppp (distributed.ppc_from_sums).  Voxels outside
+        the mask are NaN."""
+        from .distributed import ppc_from_sums
+        tr = self._trainer
+        self._check_mvn_family("posterior_predictive")
+        T = data.shape[-1]
+        x = _flat(data, T)
+        m = None if mask is None else mask.reshape(-1)
+        q, sg = self._heads_and_sigma(data, q)
+        sums, out, curves = tr._ctx.posterior_predictive(x, m, q, sg, L=no_samples, seed=seed, voxel0=voxel0,
+                                                         want_curves=want_curves)
+        lead = data.shape[:-1]
+        res = {k: out[:, i].reshape(lead) for i, k in enumerate(tr._ctx.PPC_COLUMNS)}
+        if curves is not None:
+            res.update(pred_mean=curves[..., 0].reshape(lead + (T,)), pred_sd=curves[..., 1].reshape(lead + (T,)),
+                       std_resid=curves[..., 2].reshape(lead + (T,)))
+        el, pw, pp = ppc_from_sums(sums)
+        res.update(sums=sums, mean_elpd_waic=el, mean_p_waic=pw, mean_ppp=pp)
+        return res
+
 
 class EncoderTrainer:
     def __init__(self,
@@ -696,7 +725,7 @@ class EncoderTrainer:
 
     def save_predictions(self, model, data, filename, transform_directory=None, use_first_op=True,
                          fine_tuner_model=None, priors=None, iw_samples=None, refine_steps=None,
-                         posterior_grid=None):
+                         posterior_grid=None, ppc_samples=None):
         """model.py:772-887: write `<filename>_{oef,dbv,r2p,logstds}.nii.gz` (posterior means of
         OEF / DBV / R2' over 200 draws and their variances) and, with a fine tuner,
         `_likelihood` (per-voxel NLL averaged over 100 stochastic passes), `_kl` (100-draw KL to
@@ -713,6 +742,11 @@ class EncoderTrainer:
         `_r2p_exact`, `_oef_exact_sd`, `_dbv_exact_sd`, `_oef_ci_lo`, `_oef_ci_hi`, `_dbv_ci_lo`, `_dbv_ci_hi`,
         `_logevidence_exact`, `_vigap_exact` (log p(x) - ELBO of the encoder's heads) and `_gridedge` (edge_mass),
         zero outside the mask; these maps join the returned dict.
+        ppc_samples = L (with a fine tuner; this package's addition): posterior predictive checks of L draws from the
+        encoder's heads (FineTuner.posterior_predictive) as `_ppp` (predictive p-value of the chi2 discrepancy),
+        `_elpdwaic`, `_pwaic`, `_maxresid` (largest |standardised residual|) and the per-tau `_predmean`, `_predsd`,
+        `_stdresid` [X, Y, Z, subj*T] (fitted curve, predictive sd, standardised residual in the likelihood's
+        normalised space), zero outside the mask; these maps join the returned dict.  `_residual` is unchanged.
         data [subj, X, Y, Z, T+1] with the mask last; each map is stored as [X, Y, Z, subj*C].
         `transform_directory/example.nii.gz`, when present, donates its header (:794-797); the
         FSL `applywarp`/`fslmerge` MNI step (:850-879) is preprocessing outside this package and
@@ -810,6 +844,21 @@ class EncoderTrainer:
             for k, v in grid_maps.items():
                 save_im_data(v, filename + '_' + k)
             iw_maps = dict(iw_maps or {}, **grid_maps)
+
+        if fine_tuner_model and ppc_samples:
+            pc = fine_tuner_model.posterior_predictive(data[..., :-1], mask, no_samples=int(ppc_samples),
+                                                       seed=self._seed + 53, want_curves=True)
+            live = mask[..., 0] > 0
+            zero = torch.zeros_like(pc["ppp"])
+            ppc_maps = {k: torch.where(live, v, zero)[..., None] for k, v in
+                        (("ppp", pc["ppp"]), ("elpdwaic", pc["elpd_waic"]), ("pwaic", pc["p_waic"]),
+                         ("maxresid", pc["max_abs_z"]))}
+            zt = torch.zeros_like(pc["pred_mean"])
+            ppc_maps.update({k: torch.where(live[..., None], pc[c], zt) for k, c in
+                             (("predmean", "pred_mean"), ("predsd", "pred_sd"), ("stdresid", "std_resid"))})
+            for k, v in ppc_maps.items():
+                save_im_data(v, filename + '_' + k)
+            iw_maps = dict(iw_maps or {}, **ppc_maps)
 
         save_im_data(means[..., 0:1], filename + '_oef')
         save_im_data(means[..., 1:2], filename + '_dbv')

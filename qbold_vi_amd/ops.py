@@ -551,6 +551,39 @@ class Context:
                    "qbold_posterior_grid")
         return sums, out, box
 
+    PPC_COLUMNS = ("ppp", "dbar", "lppd", "p_waic", "elpd_waic", "max_abs_z")
+
+    def posterior_predictive(self, x, mask, q, sigma, L=256, z=None, seed=1, voxel0=0, want_curves=False):
+        """Posterior predictive checks of L draws per voxel from q (qbold_posterior_predictive; Philox stream 8 unless
+        z [N, L, 2] is given), in the likelihood's own space (normalised, logged with predict_log data).  Voxels with
+        mask <= 0 come back NaN.  Returns (sums double[4] device tensor = (sum [m>0] m elpd_waic, sum [m>0] m p_waic,
+        sum [m>0] m ppp, sum [m>0] m), out [N, 6] with the columns of PPC_COLUMNS, curves [N, T, 3] = (predictive
+        mean, predictive sd, standardised residual) per tau, or None)."""
+        L = int(L)
+        if not 2 <= L <= 1 << 30:
+            raise ValueError("posterior_predictive: need 2 <= L <= 2^30")
+        for name, t in (("x", x), ("q", q), ("sigma", sigma), ("mask", mask), ("z", z)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+                raise ValueError(f"posterior_predictive: {name} must be a cuda (ROCm) tensor; there is no CPU fallback")
+        x = _f32(x, "x", self.T)
+        N = x.numel() // self.T
+        q = _f32(q, "q", 5)
+        sigma = _f32(sigma, "sigma", self.T)
+        mask = _f32(mask, "mask") if mask is not None else None
+        z = _f32(z, "z", 2) if z is not None else None
+        if z is not None and z.numel() != N * L * 2:
+            raise ValueError("z must be [N, L, 2]")
+        if q.numel() != N * 5 or sigma.numel() != N * self.T or (mask is not None and mask.numel() != N):
+            raise ValueError("posterior_predictive: q [N, 5], sigma [N, T] and mask [N] must match x [N, T]")
+        sums = torch.empty(4, dtype=torch.float64, device=x.device)
+        out = torch.empty((N, _lib.QBOLD_PPC_OUT), dtype=torch.float32, device=x.device)
+        curves = torch.empty((N, self.T, 3), dtype=torch.float32, device=x.device) if want_curves else None
+        _lib.check(self.lib.qbold_posterior_predictive(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(sigma),
+                                                       _ptr(z), L, int(seed), int(voxel0), _ptr(out), _ptr(curves),
+                                                       _ptr(sums), _ptr(self._workspace()), N, _stream()),
+                   "qbold_posterior_predictive")
+        return sums, out, curves
+
     def vi_fwd_exact(self, weights, x, mask, prior, S=1, K=70, seed=1, voxel0=0):
         """The same evaluation with the encoder on the exact-float32 layer-wise path (f32-input MFMA GEMMs,
         qbold_encoder_train_fwd) -- no f16 operand split, so no 65504 operand limit.  Slow (one launch per layer,

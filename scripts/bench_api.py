@@ -98,6 +98,10 @@ def main():
         "composed_loop(T=24,steps=100,S=4,K=70)": (lambda: composed(ctx24, x24, torch.log(sg24), 100, 4), 0),
         "posterior_grid(defaults)": (lambda: ctx.posterior_grid(x, mask, o1, sg, q=q), 8 * T + 48 + 68),
         "posterior_grid(q=None,gh=0)": (lambda: ctx.posterior_grid(x, mask, o1, sg, gh=0), 8 * T + 28 + 68),
+        "log_evidence(K=256)": (lambda: ctx.log_evidence(x, mask, q, o1, sg, 256, seed=1), 8 * T + 52),
+        "posterior_predictive(L=256)": (lambda: ctx.posterior_predictive(x, mask, q, sg, 256), 8 * T + 24 + 24),
+        "posterior_predictive(L=256,curves)": (lambda: ctx.posterior_predictive(x, mask, q, sg, 256, want_curves=True),
+                                               8 * T + 24 + 24 + 12 * T),
         "vi_fwd(S=32,K=70)": (lambda: ctx.vi_fwd(ew, x, mask, o1, 32, 70, seed=1), 4 * T + 52),
         "synth_loss_bwd": (lambda: st.synth_loss_bwd(y3, o1), 12 + 20 + 24),
         "wls_fit": (lambda: ctx.wls_fit(x), 4 * T + 12),
