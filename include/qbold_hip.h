@@ -410,6 +410,35 @@ int qbold_refine_posterior(const qbold_ctx* ctx, const float* x, const float* ma
                            const qbold_refine_cfg* cfg, uint64_t seed, int64_t voxel0,
                            float* q_out, float* loss, int64_t N, void* stream);
 
+/* The same refinement of a volume under the TV smoothness prior of the fine-tuning loss (model.py:726-754; this
+ * package's addition).  The volume is in qbold_smoothness's layout: geom {B, X, Y, Z}, voxel
+ * v = ((b X + x) Y + y) Z + z, N = B X Y Z.  The steps minimise the joint objective
+ *   F(q) = sum_{v: m_v > 0} (E_q_v[nll(x_v | .)] + KL(q_v || p_v)) + tv_weight TV(q),
+ *   TV(q) = sum over x- and y-adjacent pairs (v, n) with m_v > 0 and m_n > 0 of
+ *           |sigmoid(q_v[0]) - sigmoid(q_n[0])| + |sigmoid(q_v[2]) - sigmoid(q_n[2])|
+ * -- the first sum qbold_refine_posterior's, TV qbold_smoothness's tv_sum (no z term, as in the reference); F / sum(mask)
+ * is the reference's fine-tuning loss with kl weight 1 and the closed-form KL when tv_weight = smoothness_weight.  The
+ * subgradient of |d| is sign(d), sign(0) = 0.
+ *   Jacobi steps: at step j every voxel's gradient is taken at the step-j heads of all voxels (its own draws and KL at
+ *   its own heads, the TV subgradient against its neighbours' step-j means), then every voxel takes its own Adam / SGD
+ *   update: full-batch Adam / SGD on F, independent of how voxels map to lanes or launches.
+ *   Draws, z, the cosine schedule, cfg, loss [N][2] (the -ELBO part only), the configurations and the error codes are
+ *   qbold_refine_posterior's.  tv_weight = 0 couples nothing and runs qbold_refine_posterior itself (its bits, one
+ *   launch, the workspace unused); tv_weight > 0 runs one launch per step, whose per-voxel part agrees with
+ *   qbold_refine_posterior's arithmetic to rounding.
+ *   Voxels with mask <= 0 (or NaN) get q_in copied bit for bit and never enter a TV edge; mask NULL = all voxels in.
+ *   q_out may alias q_in.  voxel0: the global index of the volume's first voxel (the Philox key).  TV never couples
+ *   batch elements or z slices, so sharding by whole batch elements (voxel0 = b0 X Y Z) gives the same bits.
+ *   workspace: qbold_refine_spatial_workspace_bytes() bytes (88 per voxel), 16-byte aligned, not kept between calls.
+ * All work on `stream`.  QBOLD_ERR_INVALID also for a non-finite or negative tv_weight, a bad geometry,
+ * a voxel count (or workspace size) beyond int64, or a NULL or misaligned workspace. */
+int64_t qbold_refine_spatial_workspace_bytes(const qbold_ctx* ctx, const qbold_geometry* geom);
+int qbold_refine_posterior_spatial(const qbold_ctx* ctx, const float* x, const float* mask, const float* q_in,
+                                   const float* prior, const float* sigma, const float* z,
+                                   const qbold_geometry* geom, float tv_weight, int steps, int S,
+                                   const qbold_refine_cfg* cfg, uint64_t seed, int64_t voxel0,
+                                   float* q_out, float* loss, void* workspace, void* stream);
+
 /* Exact per-voxel posteriors of the fine-tuning model by quadrature on the logit plane (this package's addition; the
  * reference has no counterpart).  With sigma fixed the latent space is u = (a, b), the logits of (OEF, DBV), and
  *   J(u) = -nll(x | OEF(clip a), DBV(clip b); sigma) + log N(u; mu_p, Sigma_p)

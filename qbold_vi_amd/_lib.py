@@ -134,6 +134,9 @@ SIGNATURES = {
     "qbold_posterior_predictive": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
     "qbold_refine_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(RefineCfg), _U64,
                                          _I64, _P, _P, _I64, _P]),
+    "qbold_refine_spatial_workspace_bytes": (C.c_int64, [_P, C.POINTER(Geometry)]),
+    "qbold_refine_posterior_spatial": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(Geometry), C.c_float, C.c_int,
+                                                 C.c_int, C.POINTER(RefineCfg), _U64, _I64, _P, _P, _P, _P]),
     "qbold_vi_fwd": (C.c_int, [_P, C.POINTER(EncoderShape), _P, _P, _P, _P, C.c_int, C.c_int,
                                _U64, _I64, _P, _P, _P, _P, _I64, _P]),
 }

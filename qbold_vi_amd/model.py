@@ -297,25 +297,38 @@ class FineTuner:
         return q, sg
 
     def refine(self, data, mask, prior, steps=200, no_samples=1, lr=0.1, lr_final=None, optimizer="adam",
-               seed=1, voxel0=0):
+               seed=1, voxel0=0, smoothness_weight=0.0):
         """Semi-amortised inference (Kim et al. 2018; Cremer et al. 2018): start from the encoder heads of
         encoder_model.predict (as log_evidence() takes them) and run `steps` Adam / SGD steps on each voxel's own
         E_q[nll] + KL(q || prior), `no_samples` likelihood draws per step, sigma held fixed (the encoder's sigma head
         or the fine tuner's homoscedastic sigma), no TV term (Context.refine_posterior; lr_final None = lr / 10).
         Voxels outside the mask keep the encoder's heads.  Returns dict(q = refined raw heads shaped like the data's
         spatial dims + (5,), loss = [..., 2] (-ELBO estimate at the first step, its mean over the last tenth of the
-        steps)); q goes unchanged to calculate_means, elbo(q=...), log_evidence(q=...)."""
+        steps)); q goes unchanged to calculate_means, elbo(q=...), log_evidence(q=...).
+        smoothness_weight > 0 (image data [B, X, Y, Z, T] only): refine the volume under the fine-tuning loss's TV
+        prior as well, full-batch steps on sum(E_q[nll] + KL) + smoothness_weight TV (Context.refine_posterior_spatial;
+        the configuration's smoothness_weight gives the reference's weighting); 0 is the per-voxel refinement."""
         tr = self._trainer
         self._check_mvn_family("refine")
         T = data.shape[-1]
+        smoothness_weight = float(smoothness_weight)
+        if smoothness_weight != 0.0 and data.dim() != 5:
+            raise ValueError("refine: smoothness_weight > 0 needs image data [B, X, Y, Z, T] (the TV term needs its "
+                             f"geometry); got shape {tuple(data.shape)}")
         x = _flat(data, T)
         m = None if mask is None else mask.reshape(-1)
         p5 = _flat(prior, prior.shape[-1]).contiguous()
         q, sg = self._heads_and_sigma(data)
+        lead = data.shape[:-1]
+        if smoothness_weight != 0.0:
+            q_out, loss = tr._ctx.refine_posterior_spatial(
+                x.reshape(lead + (T,)), m, q.reshape(lead + (5,)), p5.reshape(lead + (5,)), sg.reshape(lead + (T,)),
+                smoothness_weight, steps=steps, S=no_samples, lr=lr, lr_final=lr_final, optimizer=optimizer,
+                seed=seed, voxel0=voxel0, want_loss=True)
+            return dict(q=q_out, loss=loss)
         q_out, loss = tr._ctx.refine_posterior(x, m, q, p5, sg, steps=steps, S=no_samples, lr=lr,
                                                lr_final=lr_final,
                                                optimizer=optimizer, seed=seed, voxel0=voxel0, want_loss=True)
-        lead = data.shape[:-1]
         return dict(q=q_out.reshape(lead + (5,)), loss=loss.reshape(lead + (2,)))
 
     def posterior_grid(self, data, mask, prior, q=None, **grid_kw):
@@ -725,7 +738,7 @@ class EncoderTrainer:
 
     def save_predictions(self, model, data, filename, transform_directory=None, use_first_op=True,
                          fine_tuner_model=None, priors=None, iw_samples=None, refine_steps=None,
-                         posterior_grid=None, ppc_samples=None):
+                         posterior_grid=None, ppc_samples=None, refine_smoothness_weight=0.0):
         """model.py:772-887: write `<filename>_{oef,dbv,r2p,logstds}.nii.gz` (posterior means of
         OEF / DBV / R2' over 200 draws and their variances) and, with a fine tuner,
         `_likelihood` (per-voxel NLL averaged over 100 stochastic passes), `_kl` (100-draw KL to
@@ -737,6 +750,8 @@ class EncoderTrainer:
         (FineTuner.refine) and also write `_oef_refined`, `_dbv_refined`, `_r2p_refined` (calculate_means of the
         refined heads) and `_amortgap` (per-voxel ELBO of the refined heads minus that of the encoder's, both from
         FineTuner.elbo(q=...) on the same draws; zero outside the mask); these maps join the returned dict.
+        refine_smoothness_weight (with refine_steps): FineTuner.refine's smoothness_weight -- refine the volume under
+        the TV prior of the fine-tuning loss too (5.0 in configurations/optimal.yaml); the maps keep their names.
         posterior_grid = True or a dict of grid keywords (with a fine tuner; this package's addition): the exact
         posterior by quadrature of the encoder's heads (FineTuner.posterior_grid) as `_oef_exact`, `_dbv_exact`,
         `_r2p_exact`, `_oef_exact_sd`, `_dbv_exact_sd`, `_oef_ci_lo`, `_oef_ci_hi`, `_dbv_ci_lo`, `_dbv_ci_hi`,
@@ -810,7 +825,8 @@ class EncoderTrainer:
         if fine_tuner_model and refine_steps:
             x_ft = data[..., :-1]
             p_ft = torch.as_tensor(priors, device=data.device)[..., :self._nq]
-            ref = fine_tuner_model.refine(x_ft, mask, p_ft, steps=int(refine_steps), seed=self._seed + 43)
+            ref = fine_tuner_model.refine(x_ft, mask, p_ft, steps=int(refine_steps), seed=self._seed + 43,
+                                          smoothness_weight=refine_smoothness_weight)
             q0, _ = fine_tuner_model._heads_and_sigma(x_ft)
             lead = data.shape[:4]
 

@@ -38,6 +38,24 @@ def _f32(t, name, shape_last=None):
     return t
 
 
+def _refine_cfg(what, steps, S, lr, lr_final, optimizer, betas, eps):
+    """The argument checks of the refinement entries (raised before any launch): (steps, S, Sp, qbold_refine_cfg)."""
+    if optimizer not in ("adam", "sgd"):
+        raise ValueError("optimizer must be 'adam' or 'sgd'")
+    steps, S = int(steps), int(S)
+    if steps < 1 or S < 1:
+        raise ValueError(f"{what}: need steps >= 1 and S >= 1")
+    lr = float(lr)
+    lr_final = 0.1 * lr if lr_final is None else float(lr_final)
+    if not lr > 0.0 or not lr_final >= 0.0:
+        raise ValueError(f"{what}: need lr > 0 and lr_final >= 0")
+    Sp = 4 * ((S + 3) // 4)
+    if steps * Sp // 4 >= 1 << 32:
+        raise ValueError(f"{what}: steps * 4 ceil(S / 4) / 4 must be below 2^32 (the Philox call word)")
+    cfg = _lib.RefineCfg(0 if optimizer == "adam" else 1, lr, lr_final, float(betas[0]), float(betas[1]), float(eps))
+    return steps, S, Sp, cfg
+
+
 def merge_ranges(pieces):
     """Sorted [offset, length] pieces with touching neighbours merged."""
     out = []
@@ -473,18 +491,7 @@ class Context:
         Defaults: MEASUREMENTS.md section 10.
         Returns q_out [N, 5] (raw heads, like q) and, with want_loss, loss [N, 2] = (-ELBO estimate at step 0, its
         mean over the last ceil(steps / 10) steps)."""
-        if optimizer not in ("adam", "sgd"):
-            raise ValueError("optimizer must be 'adam' or 'sgd'")
-        steps, S = int(steps), int(S)
-        if steps < 1 or S < 1:
-            raise ValueError("refine_posterior: need steps >= 1 and S >= 1")
-        lr = float(lr)
-        lr_final = 0.1 * lr if lr_final is None else float(lr_final)
-        if not lr > 0.0 or not lr_final >= 0.0:
-            raise ValueError("refine_posterior: need lr > 0 and lr_final >= 0")
-        Sp = 4 * ((S + 3) // 4)
-        if steps * Sp // 4 >= 1 << 32:
-            raise ValueError("refine_posterior: steps * 4 ceil(S / 4) / 4 must be below 2^32 (the Philox call word)")
+        steps, S, Sp, cfg = _refine_cfg("refine_posterior", steps, S, lr, lr_final, optimizer, betas, eps)
         x = _f32(x, "x", self.T)
         N = x.numel() // self.T
         q = _f32(q, "q", 5)
@@ -494,14 +501,57 @@ class Context:
         z = _f32(z, "z", 2) if z is not None else None
         if z is not None and z.numel() != N * steps * Sp * 2:
             raise ValueError("z must be [N, steps, 4 ceil(S / 4), 2]")
-        cfg = _lib.RefineCfg(0 if optimizer == "adam" else 1, lr, lr_final, float(betas[0]), float(betas[1]),
-                             float(eps))
         q_out = torch.empty((N, 5), dtype=torch.float32, device=x.device)
         loss = torch.empty((N, 2), dtype=torch.float32, device=x.device) if want_loss else None
         _lib.check(self.lib.qbold_refine_posterior(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior),
                                                    _ptr(sigma), _ptr(z), steps, S, C.byref(cfg), int(seed),
                                                    int(voxel0), _ptr(q_out), _ptr(loss), N, _stream()),
                    "qbold_refine_posterior")
+        return (q_out, loss) if want_loss else q_out
+
+    def refine_posterior_spatial(self, x5, mask5, q5, prior5, sigma5, tv_weight, steps=200, S=1, lr=0.1,
+                                 lr_final=None, optimizer="adam", betas=(0.9, 0.999), eps=1e-8, z=None, seed=1,
+                                 voxel0=0, want_loss=False):
+        """refine_posterior on a volume under the TV smoothness prior (qbold_refine_posterior_spatial): full-batch Adam
+        or SGD on sum over the mask of (E_q[nll] + KL(q || prior)) + tv_weight TV(q), TV = smoothness()'s sum over x-
+        and y-neighbour pairs inside the mask (tv_weight = the reference's smoothness_weight gives its fine-tuning
+        loss's relative weighting).  x5, sigma5 [B, X, Y, Z, T], q5, prior5 [B, X, Y, Z, 5], mask5 [B, X, Y, Z(, 1)] or
+        None (every voxel); z [B X Y Z, steps, 4 ceil(S / 4), 2] or None (Philox stream 7 keyed by voxel0 + the voxel's
+        index in the volume).  tv_weight = 0 is refine_posterior on the flattened volume, bit for bit.
+        Returns q_out [B, X, Y, Z, 5] and, with want_loss, loss [B, X, Y, Z, 2] (the -ELBO part, as refine_posterior's)."""
+        steps, S, Sp, cfg = _refine_cfg("refine_posterior_spatial", steps, S, lr, lr_final, optimizer, betas, eps)
+        tv_weight = float(tv_weight)
+        if not (math.isfinite(tv_weight) and tv_weight >= 0.0):
+            raise ValueError("refine_posterior_spatial: tv_weight must be finite and >= 0")
+        x = _f32(x5, "x", self.T)
+        if x.dim() != 5:
+            raise ValueError("refine_posterior_spatial expects x [B, X, Y, Z, T]")
+        lead = tuple(x.shape[:4])
+        N = x.numel() // self.T
+        q = _f32(q5, "q", 5)
+        prior = _f32(prior5, "prior", 5)
+        sigma = _f32(sigma5, "sigma", self.T)
+        for name, t in (("q", q), ("prior", prior), ("sigma", sigma)):
+            if tuple(t.shape[:-1]) != lead:
+                raise ValueError(f"refine_posterior_spatial: {name} is {tuple(t.shape)}, expected {lead} + (C,)")
+        mask = _f32(mask5, "mask").reshape(-1) if mask5 is not None else None
+        if mask is not None and mask.numel() != N:
+            raise ValueError("refine_posterior_spatial: mask does not match x")
+        z = _f32(z, "z", 2) if z is not None else None
+        if z is not None and z.numel() != N * steps * Sp * 2:
+            raise ValueError("z must be [B X Y Z, steps, 4 ceil(S / 4), 2]")
+        geom = Geometry(*lead)
+        nbytes = int(self.lib.qbold_refine_spatial_workspace_bytes(self.handle, C.byref(geom)))
+        if nbytes < 0:
+            raise ValueError(f"refine_posterior_spatial: geometry {lead} is too large")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        q_out = torch.empty(lead + (5,), dtype=torch.float32, device=x.device)
+        loss = torch.empty(lead + (2,), dtype=torch.float32, device=x.device) if want_loss else None
+        _lib.check(self.lib.qbold_refine_posterior_spatial(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior),
+                                                           _ptr(sigma), _ptr(z), C.byref(geom), tv_weight, steps, S,
+                                                           C.byref(cfg), int(seed), int(voxel0), _ptr(q_out),
+                                                           _ptr(loss), _ptr(ws), _stream()),
+                   "qbold_refine_posterior_spatial")
         return (q_out, loss) if want_loss else q_out
 
     GRID_COLUMNS = ("log_p", "elbo_q", "oef", "dbv", "r2p", "oef_sd", "dbv_sd", "r2p_sd", "corr", "oef_lo", "oef_hi",

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times every data-path entry point of the C ABI on 1 M voxels (HIP events on the launch stream) and
-prints one JSON object: ms per call and the algorithmic GB/s each call moves.  The headline number is
+prints one JSON object: ms per call and the algorithmic GB/s each call moves.  Arguments: name substrings to time
+only the matching calls (default: all).  The headline number is
 bench.py's; this table backs the per-kernel rows of DESIGN.md."""
 import configparser
 import json
@@ -64,6 +65,36 @@ def main():
 
     def rbytes(TT):   # x, sigma, q, prior, mask in; q out
         return 4 * (2 * TT + 10) + 4 + 20
+
+    # refinement under the TV prior (w = 5, optimal.yaml's smoothness_weight) on 1 M voxels as a 16 x 128 x 64 x 8
+    # volume and on make_synthetic_volumes.py's 4 x 96 x 96 x 8, and the loop a user composes for it today: per step
+    # qbold_elbo_bwd(S, K = 70) + qbold_smoothness(weight = w, g_q) + qbold_adamw_step on the N x 5 heads
+    def volume(B, X, Y, Z):
+        nv = B * X * Y * Z
+        r = lambda t: t[:nv].reshape(B, X, Y, Z, t.shape[-1])   # noqa: E731
+        return r(x), mask[:nv].reshape(B, X, Y, Z), r(q), r(o1), r(sg), r(ls)
+    vol1m, vol96 = volume(16, 128, 64, 8), volume(4, 96, 96, 8)
+
+    def spatial(v, steps, S, w=5.0):
+        xx, mm, qq, pp, ss, _ = v
+        return ctx.refine_posterior_spatial(xx, mm, qq, pp, ss, w, steps=steps, S=S)
+
+    def composed_tv(v, steps, S, w=5.0):
+        from qbold_vi_amd.ops import _ptr, _stream
+        xx, mm, qv, pp, _, lsx = v
+        nv = mm.numel()
+        qq = qv.clone()
+        m1, m2 = torch.zeros_like(qq), torch.zeros_like(qq)
+        for j in range(steps):
+            _, gq, _, _ = ctx.elbo_bwd(xx.reshape(nv, T), mm.reshape(nv), qq.reshape(nv, 5), pp.reshape(nv, 5),
+                                       lsx.reshape(nv, T), S, 70, seed=1 + j)
+            ctx.smoothness(qq, mm, weight=w, g_q=gq)
+            ctx.lib.qbold_adamw_step(ctx.handle, _ptr(qq), _ptr(gq), _ptr(m1), _ptr(m2), 5 * nv, 0.05, 0.9, 0.999,
+                                     1e-8, 0.0, j + 1, _stream())
+        return qq
+
+    def sbytes(TT):   # per step: x, sigma, heads, moments, loss, prior, mask, neighbours' heads 0, 2 and masks in; 68 out
+        return 4 * (2 * TT + 21) + 68
     calls = {
         # name: (callable, algorithmic bytes per voxel)
         "signal_fwd": (lambda: ctx.signal_fwd(y), 8 + 4 * T),
@@ -96,6 +127,18 @@ def main():
         "composed_loop(T=11,steps=100,S=4,K=70)": (lambda: composed(ctx, x, ls, 100, 4), 0),
         "composed_loop(T=24,steps=200,S=1,K=70)": (lambda: composed(ctx24, x24, torch.log(sg24), 200, 1), 0),
         "composed_loop(T=24,steps=100,S=4,K=70)": (lambda: composed(ctx24, x24, torch.log(sg24), 100, 4), 0),
+        "refine_posterior_spatial(T=11,steps=200,S=1,w=5,16x128x64x8)": (lambda: spatial(vol1m, 200, 1),
+                                                                         200 * sbytes(T)),
+        "refine_posterior_spatial(T=11,steps=200,S=1,w=0,16x128x64x8)": (lambda: spatial(vol1m, 200, 1, 0.0),
+                                                                         200 * sbytes(T)),
+        "composed_loop_tv(T=11,steps=200,S=1,K=70,w=5,16x128x64x8)": (lambda: composed_tv(vol1m, 200, 1), 0),
+        "refine_posterior_spatial(T=11,steps=200,S=1,w=5,4x96x96x8)": (lambda: spatial(vol96, 200, 1),
+                                                                       200 * sbytes(T) * 294912 / n),
+        "refine_posterior(T=11,steps=200,S=1,4x96x96x8)": (
+            lambda: ctx.refine_posterior(vol96[0].reshape(-1, T), vol96[1].reshape(-1), vol96[2].reshape(-1, 5),
+                                         vol96[3].reshape(-1, 5), vol96[4].reshape(-1, T), 200, 1),
+            rbytes(T) * 294912 / n),
+        "composed_loop_tv(T=11,steps=200,S=1,K=70,w=5,4x96x96x8)": (lambda: composed_tv(vol96, 200, 1), 0),
         "posterior_grid(defaults)": (lambda: ctx.posterior_grid(x, mask, o1, sg, q=q), 8 * T + 48 + 68),
         "posterior_grid(q=None,gh=0)": (lambda: ctx.posterior_grid(x, mask, o1, sg, gh=0), 8 * T + 28 + 68),
         "log_evidence(K=256)": (lambda: ctx.log_evidence(x, mask, q, o1, sg, 256, seed=1), 8 * T + 52),
@@ -111,8 +154,11 @@ def main():
         "encoder_spatial_fwd(3x3x1)": (lambda: st.forward_spatial(x5), None),
         "adamw_step(146k params)": (lambda: st.adamw(1e-3, 1e-4), None),
     }
+    only = [a for a in sys.argv[1:] if not a.startswith("-")]   # name substrings: time only the matching calls
     out = {}
     for name, (fn, bpv) in calls.items():
+        if only and not any(o in name for o in only):
+            continue
         import time
         t0 = time.perf_counter()   # clock ramp: ~20 ms of load before an idle MI355X runs at sustained clocks
         while time.perf_counter() - t0 < 0.1:
