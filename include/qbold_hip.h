@@ -382,6 +382,30 @@ int qbold_log_evidence_fwd(const qbold_ctx* ctx, const float* x, const float* ma
                            int64_t voxel0, float* out, float* is_means, double* sums, void* workspace,
                            int64_t N, void* stream);
 
+/* Gradient of the importance-weighted bound above with respect to the encoder's head outputs, for fine-tuning the encoder
+ * on it (this package's addition; the reference trains on the ELBO only).  Per voxel the K draws of
+ * qbold_log_evidence_fwd (explicit z [N][K][2], or the Philox stream 6 keyed (seed, voxel0 + i): the same draws for the
+ * same seed), u_k = mu + L eps_k, log w_k as there, w~_k = softmax_k(log w), loss l_v = -(logsumexp_k log w_k - log K).
+ *   log_sigma [N][T]: the sigma head BEFORE exp, as qbold_elbo_bwd takes it
+ *   g_log_sigma [N][T] = m_v sum_k w~_k d nll_k / d log sigma_t   (the exact gradient of l_v for fixed eps)
+ *   g_q [N][5] = m_v sum_k w~_k^2 (d nll_k / du + d (log q - log p)_k / du, q held inside log q) du_k / dq_raw: the
+ *     doubly-reparameterised gradient (DReG, Tucker et al. 2019), chained to the raw heads as qbold_elbo_bwd chains
+ *     its own, clipped draws included.  At K = 1 and m in {0, 1} it is qbold_elbo_bwd's gradient of m nll + KL with
+ *     the KL drawn at the likelihood's draw.
+ *   Both UNNORMALISED by sum(m), like qbold_elbo_bwd's; voxels with mask <= 0 (or NaN) get exact zeros and add nothing
+ *   to the sums; mask NULL = ones.
+ *   out [N][3] or NULL: qbold_log_evidence_fwd's columns (log p^, ELBO_same, ESS)
+ *   sums: DEVICE double[3] = (sum_{m>0} m (-log p^), sum_{m>0} m (-ELBO_same), sum_{m>0} m), overwritten: [2] is the
+ *     normaliser qbold_encoder_train_bwd / qbold_encoder_spatial_bwd read
+ *   workspace: qbold_elbo_workspace_bytes() bytes.
+ * Fixed-order sums, no atomics: a voxel's outputs are the same bits at any batch position, under any sharding by voxel0
+ * and run to run.  Configurations of qbold_elbo_bwd (full model, table mode, T = 11 or 24), the use_mvg = True family;
+ * QBOLD_ERR_UNSUPPORTED otherwise.  QBOLD_ERR_INVALID for K < 1, K > QBOLD_IW_MAX_K or a NULL required buffer. */
+int qbold_log_evidence_bwd(const qbold_ctx* ctx, const float* x, const float* mask, const float* q,
+                           const float* prior, const float* log_sigma, const float* z, int K, uint64_t seed,
+                           int64_t voxel0, float* g_q, float* g_log_sigma, float* out, double* sums,
+                           void* workspace, int64_t N, void* stream);
+
 /* Semi-amortised inference (Kim et al. 2018; Cremer et al. 2018): refine each voxel's posterior, starting from given
  * encoder heads, by `steps` gradient steps on that voxel's own objective
  *   E_q[nll(x | y)] + KL(q || prior)   (exact closed-form KL of the logit-space Gaussians, sigma fixed, no TV term)

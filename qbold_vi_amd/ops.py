@@ -482,6 +482,31 @@ class Context:
                    "qbold_log_evidence_fwd")
         return sums, out, means
 
+    def log_evidence_bwd(self, x, mask, q, prior, log_sigma, K, z=None, seed=1, voxel0=0, want_out=False):
+        """Head gradients of the per-voxel negative importance-weighted bound -log p^_K (qbold_log_evidence_bwd; the K
+        draws of log_evidence for the same seed, Philox stream 6 unless z [N, K, 2] is given): the doubly-reparameterised
+        gradient for q, the exact one for log_sigma (the sigma head before exp), both unnormalised by sum(mask) like
+        elbo_bwd's.  Returns (sums double[3] device tensor = (sum [m>0] m (-log p^), sum [m>0] m (-ELBO_same),
+        sum [m>0] m), g_q [N, 5], g_log_sigma [N, T], out [N, 3] = (log p^, same-draw ELBO, ESS) or None)."""
+        x = _f32(x, "x", self.T)
+        N = x.numel() // self.T
+        q = _f32(q, "q", 5)
+        prior = _f32(prior, "prior", 5)
+        ls = _f32(log_sigma, "log_sigma", self.T)
+        mask = _f32(mask, "mask") if mask is not None else None
+        z = _f32(z, "z", 2) if z is not None else None
+        if z is not None and z.numel() != N * K * 2:
+            raise ValueError("z must be [N, K, 2]")
+        sums = torch.empty(3, dtype=torch.float64, device=x.device)
+        gq = torch.empty((N, 5), dtype=torch.float32, device=x.device)
+        gls = torch.empty((N, self.T), dtype=torch.float32, device=x.device)
+        out = torch.empty((N, 3), dtype=torch.float32, device=x.device) if want_out else None
+        _lib.check(self.lib.qbold_log_evidence_bwd(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior), _ptr(ls),
+                                                   _ptr(z), int(K), int(seed), int(voxel0), _ptr(gq), _ptr(gls),
+                                                   _ptr(out), _ptr(sums), _ptr(self._workspace()), N, _stream()),
+                   "qbold_log_evidence_bwd")
+        return sums, gq, gls, out
+
     def refine_posterior(self, x, mask, q, prior, sigma, steps=200, S=1, lr=0.1, lr_final=None, optimizer="adam",
                          betas=(0.9, 0.999), eps=1e-8, z=None, seed=1, voxel0=0, want_loss=False):
         """Semi-amortised refinement of each voxel's heads (qbold_refine_posterior): `steps` Adam or SGD steps on the

@@ -312,6 +312,30 @@ def _elbo_bwd(trainer, x, mask, q, prior5, ls, S, K, seed, voxel0):
     return sums, gq, gls
 
 
+def _iw_samples(config_dict, trainer, full_model):
+    """The config's iw_samples (default 0: the reference's ELBO), checked before any step.  K > 0 fine-tunes on the
+    K-sample importance-weighted bound, -log p^_K, with the doubly-reparameterised gradient (Context.log_evidence_bwd):
+    K replaces mc_samples and kl_samples in the objective."""
+    K = int(_get(config_dict, "iw_samples", 0) or 0)
+    if K < 0:
+        raise ValueError(f"iw_samples must be >= 0, got {K}")
+    if K > 0:
+        full_model._check_mvn_family("fine-tuning on the importance-weighted bound (iw_samples > 0)")
+        if trainer._no_samples > 1:
+            raise ValueError("iw_samples > 0 replaces mc_samples and kl_samples in the objective: "
+                             f"set mc_samples to 1 (got {trainer._no_samples})")
+    return K
+
+
+def _head_grads(trainer, iw, x, mask, q, prior5, ls, S, K, seed, voxel0):
+    """(sums, g_q, g_log_sigma) of the fine-tuning objective: _elbo_bwd's, or with iw > 0 those of -log p^_iw, whose
+    sums (sum m (-log p^), sum m (-ELBO_same), sum m) the loops reduce and normalise as the ELBO's."""
+    if iw > 0:
+        sums, gq, gls, _ = trainer.context.log_evidence_bwd(x, mask, q, prior5, ls, iw, seed=seed, voxel0=voxel0)
+        return sums, gq, gls
+    return _elbo_bwd(trainer, x, mask, q, prior5, ls, S, K, seed, voxel0)
+
+
 def prepare_voxel_dataset(data, mask, model):
     """Voxel-batch counterpart of train.prepare_dataset (train.py:17-72): data are masked, the
     stream-1 output of the (pre-trained) model is the per-voxel prior."""
@@ -359,7 +383,7 @@ class CropDataset:
 
 
 def _train_full_model_crops(config_dict, trainer, full_model, study_dataset, train_dataset, log,
-                            steps_per_epoch, kl_samples, max_steps):
+                            steps_per_epoch, kl_samples, max_steps, iw=0):
     rank, world, _ = qd.init_from_env()
     ctx = trainer.context
     model = full_model.encoder_model
@@ -384,8 +408,8 @@ def _train_full_model_crops(config_dict, trainer, full_model, study_dataset, tra
             q, ls = state.forward_spatial(x5)
             if sigma_opt:
                 ls = torch.full_like(ls, sigma_opt.value)
-            sums, gq, gls = _elbo_bwd(trainer, x5.reshape(n, -1), m5.reshape(n), q, p5.reshape(n, 5), ls, S,
-                                      kl_samples, 1000 + step, rank * n)
+            sums, gq, gls = _head_grads(trainer, iw, x5.reshape(n, -1), m5.reshape(n), q, p5.reshape(n, 5), ls, S,
+                                        kl_samples, 1000 + step, rank * n)
             tv = ctx.smoothness(q.reshape(m5.shape + (5,)), m5, weight=sw, g_q=gq)
             red = torch.cat([sums, tv] + ([gls.sum(dtype=torch.float64).reshape(1)] if sigma_opt else []))
             qd.allreduce_(red, "allreduce_sums")
@@ -407,11 +431,15 @@ def _train_full_model_crops(config_dict, trainer, full_model, study_dataset, tra
                 break
         nll, kl, smooth = float(tot[0] / tot[2]), float(tot[1] / tot[2]), float(tot[3] / tot[2])
         _check_finite(nll + kl + smooth, "fine-tuning loss")
-        metrics = {"epoch": epoch, "loss": nll + kl + sw * smooth, "predicted_images_loss": nll,
-                   "predictions_loss": kl + sw * smooth, "predictions_smoothness_metric": smooth,
-                   "predictions_kl_metric": kl}
+        if iw > 0:   # tot = (sum m (-log p^), sum m (-ELBO_same), sum m, TV)
+            metrics = {"epoch": epoch, "loss": nll + sw * smooth, "iw_elbo_same": kl,
+                       "predictions_smoothness_metric": smooth}
+        else:
+            metrics = {"epoch": epoch, "loss": nll + kl + sw * smooth, "predicted_images_loss": nll,
+                       "predictions_loss": kl + sw * smooth, "predictions_smoothness_metric": smooth,
+                       "predictions_kl_metric": kl}
         # ELBOCallback (train.py:329-357): 4 validation batches, NLL averaged over 10 stochastic passes
-        vn = vk = vs = 0.0
+        vn = vk = vs = vl = 0.0
         for b in range(4):
             x5, m5, p5 = study_dataset.next_batch(gv)
             nll_b = 0.0
@@ -421,9 +449,14 @@ def _train_full_model_crops(config_dict, trainer, full_model, study_dataset, tra
             vn += nll_b / 10.0
             vk += float(out["kl"])
             vs += float(ctx.smoothness(_pad5(out["q"]).reshape(m5.shape + (5,)), m5)[0] / m5.sum())
+            if iw > 0:   # the bound on the same validation crops, its own draws
+                vl += float(full_model.log_evidence(x5, m5, p5, no_samples=iw, seed=9000 + 100 * epoch + b)
+                            ["mean_log_evidence"])
         vn, vk, vs = vn / 4, vk / 4, vs / 4
         metrics.update({"val_nll": vn, "val_elbo": vn + vk, "val_elbo_smooth": vn + vk * 1.0 + vs * sw,
                         "val_smoothness": vs, "val_smoothness_scaled": vs * sw, "val_kl": vk})
+        if iw > 0:
+            metrics["val_log_evidence"] = vl / 4
         # evaluations whose split-f16 encoder left its operand range and were recomputed on the exact-float32
         # path (ops.Context.vi_fwd, range_check): cumulative count, 0 in a healthy run
         metrics["range_fallbacks"] = int(getattr(trainer.context, "range_fallbacks", 0))
@@ -440,9 +473,10 @@ def train_full_model(config_dict, trainer, full_model, study_dataset, train_data
     assert isinstance(trainer, EncoderTrainer)
     rank, world, _ = qd.init_from_env()
     log = log or MetricsLog(rank=rank)
+    iw = _iw_samples(config_dict, trainer, full_model)
     if isinstance(train_dataset, CropDataset):
         return _train_full_model_crops(config_dict, trainer, full_model, study_dataset, train_dataset, log,
-                                       steps_per_epoch, kl_samples, max_steps)
+                                       steps_per_epoch, kl_samples, max_steps, iw)
     ctx = trainer.context
     model = full_model.encoder_model
     state = TrainState(ctx, model.weights)
@@ -471,7 +505,7 @@ def train_full_model(config_dict, trainer, full_model, study_dataset, train_data
             q2, ls = state.forward(xb, 2)
             if sigma_opt:
                 ls = torch.full_like(ls, sigma_opt.value)
-            sums, gq, gls = _elbo_bwd(trainer, xb, mb, q2, pb, ls, S, kl_samples, 1000 + step, a)
+            sums, gq, gls = _head_grads(trainer, iw, xb, mb, q2, pb, ls, S, kl_samples, 1000 + step, a)
             if sigma_opt:   # d loss / d log sigma = sum over voxels and taus of the per-tau gradients / sum(mask)
                 sums = torch.cat([sums, gls.sum(dtype=torch.float64).reshape(1)])
             qd.allreduce_sums(sums)          # global sum(mask) before the gradient is normalised
@@ -494,9 +528,14 @@ def train_full_model(config_dict, trainer, full_model, study_dataset, train_data
                 break
         nll, kl = float(tot[0] / tot[2]), float(tot[1] / tot[2])
         _check_finite(nll + kl, "fine-tuning loss")
-        metrics = {"epoch": epoch, "loss": nll + kl, "predicted_images_loss": nll, "predictions_loss": kl}
+        if iw > 0:   # tot = (sum m (-log p^), sum m (-ELBO_same), sum m)
+            metrics = {"epoch": epoch, "loss": nll, "iw_elbo_same": kl}
+        else:
+            metrics = {"epoch": epoch, "loss": nll + kl, "predicted_images_loss": nll, "predictions_loss": kl}
         metrics.update(validation_elbo(config_dict, trainer, full_model, (vx, vmask, vprior), kl_samples,
                                        seed=epoch))
+        if iw > 0 and vx.shape[0] > 0:
+            metrics["val_log_evidence"] = validation_log_evidence(full_model, (vx, vmask, vprior), iw, seed=epoch)
         metrics["range_fallbacks"] = int(getattr(trainer.context, "range_fallbacks", 0))   # see _train_full_model_crops
         log.log(metrics)
         if max_steps and step >= max_steps:
@@ -524,6 +563,16 @@ def validation_elbo(config_dict, trainer, full_model, study_dataset, kl_samples=
     sw = float(_get(config_dict, "smoothness_weight", 0.0) or 0.0)
     return {"val_nll": nll, "val_elbo": nll + kl, "val_elbo_smooth": nll + kl * 1.0 + 0.0 * sw,
             "val_smoothness": 0.0, "val_smoothness_scaled": 0.0, "val_kl": kl}
+
+
+def validation_log_evidence(full_model, study_dataset, K, seed=0):
+    """Mean log p^_K over the validation voxels (FineTuner.log_evidence, K = iw_samples, its own draws per epoch):
+    the objective of iw_samples > 0 fine-tuning, logged beside the unchanged val_* keys."""
+    vx, vmask, vprior = study_dataset
+    a, b = qd.shard_range(vx.shape[0], *qd.init_from_env()[:2])
+    out = full_model.log_evidence(vx[a:b], vmask[a:b], vprior[a:b], no_samples=K, seed=9000 + seed, voxel0=a)
+    s = qd.allreduce_sums(out["sums"].clone())
+    return float(-s[0] / s[2])
 
 
 # ----------------------------------------------------------------------------------------------

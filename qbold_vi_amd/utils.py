@@ -61,6 +61,9 @@ def setup_argparser(defaults_dict):
                    help='fine-tune / evaluate on N synthetic voxels instead of the real .npy volumes')
     p.add_argument('--mc_samples', type=int, default=1, help='likelihood draws per voxel (no_samples)')
     p.add_argument('--devices', type=int, default=1, help='GPUs (one process each, torchrun)')
+    p.add_argument('--iw_samples', type=int, default=0,
+                   help='fine-tune on the K-sample importance-weighted bound (DReG gradients) instead of the ELBO; '
+                        '0 = the ELBO')
     return p
 
 

@@ -112,6 +112,20 @@ def main():
         "kl_diag(+grad)": (lambda: ctx.kl_diag(q, o1, mask, g_q=gq0), 44 + 40),
         "elbo_fwd(S=32,K=70)": (lambda: ctx.elbo_fwd(x, mask, q, o1, sg, 32, 70, seed=1), 8 * T + 52),
         "elbo_bwd(S=1,K=70)": (lambda: ctx.elbo_bwd(x, mask, q, o1, ls, 1, 70, seed=1), 12 * T + 72),
+        # gradient of the importance-weighted bound (DReG) against the ELBO backward; bytes: x, log sigma, q, prior,
+        # mask in, g_q, g_log_sigma out
+        "elbo_bwd(S=8,K=8)": (lambda: ctx.elbo_bwd(x, mask, q, o1, ls, 8, 8, seed=1), 12 * T + 72),
+        "log_evidence_bwd(T=11,K=1)": (lambda: ctx.log_evidence_bwd(x, mask, q, o1, ls, 1, seed=1), 12 * T + 64),
+        "log_evidence_bwd(T=11,K=8)": (lambda: ctx.log_evidence_bwd(x, mask, q, o1, ls, 8, seed=1), 12 * T + 64),
+        "log_evidence_bwd(T=11,K=32)": (lambda: ctx.log_evidence_bwd(x, mask, q, o1, ls, 32, seed=1), 12 * T + 64),
+        "elbo_bwd(T=24,S=1,K=70)": (lambda: ctx24.elbo_bwd(x24, mask, q, o1, torch.log(sg24), 1, 70, seed=1),
+                                    12 * 24 + 72),
+        "log_evidence_bwd(T=24,K=1)": (lambda: ctx24.log_evidence_bwd(x24, mask, q, o1, torch.log(sg24), 1, seed=1),
+                                       12 * 24 + 64),
+        "log_evidence_bwd(T=24,K=8)": (lambda: ctx24.log_evidence_bwd(x24, mask, q, o1, torch.log(sg24), 8, seed=1),
+                                       12 * 24 + 64),
+        "log_evidence_bwd(T=24,K=32)": (lambda: ctx24.log_evidence_bwd(x24, mask, q, o1, torch.log(sg24), 32,
+                                                                       seed=1), 12 * 24 + 64),
         # importance-weighted evidence against the ELBO kernel on the same draws' forward-model work (S = K = K_iw)
         "log_evidence(K=64)": (lambda: ctx.log_evidence(x, mask, q, o1, sg, 64, seed=1), 8 * T + 52),
         "elbo_fwd(S=64,K=64)": (lambda: ctx.elbo_fwd(x, mask, q, o1, sg, 64, 64, seed=1), 8 * T + 52),

@@ -16,9 +16,11 @@ from qbold_vi_amd.training import get_params  # noqa: E402
 
 
 def measure(voxels=1 << 20, crops=(38, 25, 25, 8), steps=10, S=1, K=70, graph=True, only=None, ksel=0,
-            config_dir="config"):
-    """ms per fine-tuning step on a voxel batch and on a crop batch (bench.py embeds this in its JSON line)."""
-    a = argparse.Namespace(voxels=voxels, crops=list(crops), steps=steps, S=S, K=K, graph=graph, only=only, ksel=ksel)
+            config_dir="config", iw_samples=0):
+    """ms per fine-tuning step on a voxel batch and on a crop batch (bench.py embeds this in its JSON line).
+    iw_samples > 0: the step of iw_samples fine-tuning (qbold_log_evidence_bwd instead of qbold_elbo_bwd)."""
+    a = argparse.Namespace(voxels=voxels, crops=list(crops), steps=steps, S=S, K=K, graph=graph, only=only, ksel=ksel,
+                           iw_samples=iw_samples)
     return _run(a, config_dir)
 
 
@@ -32,6 +34,8 @@ def main():
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--only", choices=["voxel", "crop"], default=None)
     ap.add_argument("--ksel", type=int, default=0, help="qbold_ctx_set_kernel_selection mask (QBOLD_KSEL_* of include/qbold_hip.h)")
+    ap.add_argument("--iw-samples", type=int, default=0, dest="iw_samples",
+                    help="K > 0: head gradients of the K-sample importance-weighted bound (training's iw_samples)")
     a = ap.parse_args()
     print(json.dumps(_run(a, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "config"))))
 
@@ -67,9 +71,14 @@ def _run(a, config_dir):
     prior = ctx.encoder_fwd(ew, x, want=("out1",))[0]
     mask = torch.ones(N, device="cuda")
 
+    def head_grads(xx, mm, q, pp, ls):
+        if a.iw_samples > 0:
+            return ctx.log_evidence_bwd(xx, mm, q, pp, ls, a.iw_samples, seed=st.step)
+        return ctx.elbo_bwd(xx, mm, q, pp, ls, a.S, a.K, seed=st.step)
+
     def voxel_step():
         q, ls = st.forward(x, 2)
-        sums, gq, gls, _ = ctx.elbo_bwd(x, mask, q, prior, ls, a.S, a.K, seed=st.step)
+        sums, gq, gls, _ = head_grads(x, mask, q, prior, ls)
         st.backward(2, gq, gls, sums)
         st.adamw(5e-3, 2e-4, 0.9, 0.9, 1e-7)
 
@@ -85,7 +94,7 @@ def _run(a, config_dir):
 
     def crop_step():
         q, ls = st.forward_spatial(x5)
-        sums, gq, gls, _ = ctx.elbo_bwd(x5.reshape(V, -1), m5.reshape(V), q, p5, ls, a.S, a.K, seed=st.step)
+        sums, gq, gls, _ = head_grads(x5.reshape(V, -1), m5.reshape(V), q, p5, ls)
         ctx.smoothness(q.reshape(B, X, Y, Z, 5), m5, weight=5.0, g_q=gq)
         st.backward_spatial(gq, gls, sums)
         st.adamw(5e-3, 2e-4, 0.9, 0.9, 1e-7)

@@ -2,7 +2,9 @@
 """Drop-in for the reference's `python train.py configurations/optimal.yaml [-d DATA -f SYNTH]`
 (train.py:454-491): same positional YAML / argparse flags / INI `config` in the CWD.  New flags:
 --synthetic_voxels N (fine-tune on N synthetic voxels instead of the real .npy volumes),
---mc_samples S, --devices G (launch with torchrun for G > 1)."""
+--mc_samples S, --devices G (launch with torchrun for G > 1), --iw_samples K (fine-tune the encoder on the
+K-sample importance-weighted bound with doubly-reparameterised gradients instead of the ELBO; 0, the default, keeps
+the ELBO)."""
 import sys
 
 import numpy as np
