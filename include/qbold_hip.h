@@ -579,7 +579,11 @@ int qbold_encoder_train_fwd_fused(const qbold_ctx* ctx, const qbold_encoder_shap
  * side), 2 also t and r (the same launch accumulates the block's weight gradients). */
 int qbold_encoder_train_bwd_recomputes(const qbold_ctx* ctx, const qbold_encoder_shape* shape, int64_t N);
 /* The same on image crops: geom->B*X*Y*Z voxels, stream 2 with its 3x3x1 'same' convolutions
- * (shape->spatial_taps must be 9).  geom = NULL is the voxel-batch call above. */
+ * (shape->spatial_taps must be 9).  geom = NULL is the voxel-batch call above.  For U % 4 == 0 the convolutions run on
+ * split-f16 operands: an input activation beyond 65504 (or a NaN one) makes the output row of every voxel whose 3x3
+ * neighbourhood reads it NaN, and the relus of the later layers keep the NaN, so the affected voxels' q and log sigma
+ * come out NaN -- never a clamped number; other voxels and other batch elements are unaffected.  (A weight beyond
+ * 65504 has no such guard here: keep the convolution kernels inside f16's range.) */
 int qbold_encoder_spatial_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* shape, const float* weights,
                               const float* x, const qbold_geometry* geom, float* workspace, float* out_q,
                               float* out_log_sigma, void* stream);
@@ -601,10 +605,12 @@ int qbold_smoothness(const qbold_ctx* ctx, const float* q, const float* mask, co
  * of the layer-wise forward bit for bit select QBOLD_KSEL_LAYERWISE_BWD.
  * Operand range of the layer-wise backward (crops, and voxel batches under QBOLD_KSEL_LAYERWISE_BWD): the 3x3x1
  * backward-data products and the weight gradients run on split-f16 operands.  Deltas are NOT bound by f16's range:
- * with `sums` given the backward-data products lift them by 2^floor(log2 sums[2]) (exact), and the weight-gradient
- * kernels keep a running power-of-two scale per wave that follows the largest |delta| seen (accumulators rescaled,
- * exact), whatever the caller's normalisation.  Activations are taken as they are: the forward's limit above applies
- * (an activation beyond 65504 gives non-finite gradients, never a clamp), and an activation below 2^-14 in magnitude
+ * the backward-data products keep a running power-of-two scale per voxel and the weight-gradient kernels one per wave,
+ * each following the largest |delta| seen (accumulators rescaled, exact; a scale starts at 2^126, so deltas from
+ * about 2^-112 up to 1e30 keep float32-grade precision), with or without `sums` -- tested against a float64 VJP for
+ * head gradients 2^k g, |k| <= 60, and per-voxel magnitudes from 1e-9 to 1e6 in one batch.  Activations are taken as
+ * they are: the forwards' limit applies (an activation beyond 65504 makes the affected heads NaN, never a clamped
+ * number: qbold_encoder_spatial_fwd above), and an activation below 2^-14 in magnitude
  * keeps an absolute 2^-25 in the weight gradients.  QBOLD_KSEL_DW_BF16_PIECES (three bfloat16 pieces per operand, no
  * range at all) and QBOLD_KSEL_DW_EXACT_F32 select the other forms. */
 int qbold_encoder_train_bwd(const qbold_ctx* ctx, const qbold_encoder_shape* shape, const float* weights,

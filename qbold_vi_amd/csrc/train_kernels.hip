@@ -28,12 +28,23 @@ using qb::f32x4;
 // added as 64-bit FIXED-POINT integers: integer addition is associative, so the result does not depend on the order the
 // workgroups arrive in -- a floating-point atomicAdd would make these the only sums of the library that are not
 // reproducible bit for bit.  fixed_to_double_kernel turns the integers into doubles in place.
+// A non-finite partial (llrint of it is undefined) does not add: it sets the accumulator to kFixedNonFinite, which no
+// finite sum reaches (they stay below 2^60 in magnitude) and finite partials added after it cannot bring below 2^61;
+// fixed_to_double_kernel turns such a word into NaN.  However many partials are non-finite, the word stays flagged.
+constexpr long long kFixedNonFinite = 1ll << 62;
 __device__ __forceinline__ void atomic_add_fixed(double* acc, double v, double scale) {
-    atomicAdd(reinterpret_cast<unsigned long long*>(acc), (unsigned long long)llrint(v * scale));
+    const double s = v * scale;
+    if (fabs(s) < 1.0e18)   // false for NaN and +-inf
+        atomicAdd(reinterpret_cast<unsigned long long*>(acc), (unsigned long long)llrint(s));
+    else
+        atomicExch(reinterpret_cast<unsigned long long*>(acc), (unsigned long long)kFixedNonFinite);
 }
 __global__ void fixed_to_double_kernel(double* p, int n, double inv_scale) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) p[k] = (double)(*reinterpret_cast<const long long*>(p + k)) * inv_scale;
+    if (k < n) {
+        const long long f = *reinterpret_cast<const long long*>(p + k);
+        p[k] = f >= kFixedNonFinite / 2 ? NAN : (double)f * inv_scale;
+    }
 }
 constexpr double kTvFixed = 4294967296.0;      // 2^32: a TV sum is < 2^25 (N < 2^23 voxels, four unit differences each)
 constexpr double kStatsFixed = 16777216.0;     // 2^24: |sum log v|, sum 1 / v < 2^35
@@ -96,11 +107,29 @@ __device__ __forceinline__ int64_t gather_row(const Gather& gt, int64_t v) {
 // Row tensors read through a buffer resource of N x 256 bytes: an offset at or beyond kOutside is outside any of
 // them (N < 2^23) and the hardware returns zeros for it -- padding without a select behind the load.
 constexpr uint32_t kOutside = 0x80000000u;
-// one v_max_f32 (fmaxf would quiet a signalling NaN first: two instructions per value)
-__device__ __forceinline__ float max_1op(float x, float floor) {
+// relu on the rows as they arrive (floor 0) or nothing (floor -inf) in one v_maximum3_f32: unlike v_max_f32 it keeps a
+// NaN, which is how an overflowed operand (below) reaches the heads through the relus of the later layers
+__device__ __forceinline__ float max_keep_nan(float x, float floor) {
     float y;
-    asm("v_max_f32 %0, %1, %2" : "=v"(y) : "s"(floor), "v"(x));
+    asm("v_maximum3_f32 %0, %1, %2, %2" : "=v"(y) : "v"(x), "s"(floor));
     return y;
+}
+// amax = maximum(amax, |a|, |b|), NaN-propagating: a NaN operand counts as out of range
+__device__ __forceinline__ void amax_pair_nan(float& amax, float a, float b) {
+    asm("v_maximum3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(a), "v"(b));
+}
+// The delta scales start at 2^126 (1 / 2^126 is still a normal float), so deltas that all lie below 2^-112 keep them at
+// the top of f16's range instead of under its subnormals; anything larger trips the data-driven scale at its first step.
+constexpr int kDeltaScale0Exp = 126;
+constexpr float kDeltaScale0 = 8.507059173023461586e37f;   // 2^126
+constexpr float kDeltaTrip = 16384.0f;                      // 2^14: f16 ends at 65504
+// amax = max(amax, |a|, |b|) in one v_max3_f32 (encoder_core.h, split_act)
+__device__ __forceinline__ void amax_pair(float& amax, float a, float b) {
+#if QB_AMAX_ASM
+    asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(amax) : "v"(a), "v"(b));
+#else
+    amax = fmaxf(amax, fmaxf(fabsf(a), fabsf(b)));
+#endif
 }
 __device__ __forceinline__ float relu_1op(float x) {
     float y;
@@ -921,17 +950,17 @@ __global__ __launch_bounds__(1024) void conv9_kernel(const float* __restrict__ X
 // MFMAs; this one 9 x 24 x 16 = 3.5 k matrix-pipe cycles plus the operand splits.  The nine tap kernels are
 // converted once per workgroup into the weight image of encoder_core.h (9 x 16 KiB of LDS); a lane owns one
 // voxel: its crop coordinates are split once per tile, every tap reads the neighbour's row (or zeros).
-// SCALED (the backward-data launches): the rows are deltas that carry the loss's 1 / sum(mask) -- 1e-6 and below, where
-// an f16 high half is subnormal or zero.  They are multiplied by 2^floor(log2 sum(mask)) on arrival (in place of the
-// forward's relu-on-arrival: the same instruction count) and the outputs by its inverse: exact both ways, and the
-// split sees the per-voxel gradients at their own magnitude, whatever the batch size.
+// SCALED (the backward-data launches): the rows are deltas, of any magnitude (they carry the loss's 1 / sum(mask), and an
+// outlier under a small sigma reaches 1e5 at the heads already), where a fixed f16 split overflows or loses them under its
+// subnormals.  Each voxel keeps a running power-of-two scale instead: the largest |delta| of its neighbour rows seen so
+// far lands in [2^11, 2^12) (its four lanes agree on it), a tap that raises it rescales the voxel's accumulators (exact),
+// and the outputs take its inverse.  It depends on the voxel's data only; inf / NaN deltas pass unscaled.
 template <bool SCALED>
 __global__ __launch_bounds__(1024) void conv9h_kernel(const float* __restrict__ X, int ldx, int U,
                                                       const float* __restrict__ K9, int flip,
                                                       const float* __restrict__ b, float* __restrict__ Y,
                                                       int ldy, int act, const float* __restrict__ mask,
-                                                      int ldm, int64_t N, Gather g0,
-                                                      const double* __restrict__ sums) {
+                                                      int ldm, int64_t N, Gather g0) {
     extern __shared__ __align__(16) float img[];  // [9][s 2][m 4][hi, lo][lane 64][8 halves], then bias[64]
     float* bias = img + 9 * 4096;
     // the nine tap kernels into the weight image: thread (a, b) of a 16 x 64 patch reads W[tap][a][b] (rows of U
@@ -976,17 +1005,6 @@ __global__ __launch_bounds__(1024) void conv9h_kernel(const float* __restrict__ 
 #pragma unroll
     for (int q = 0; q < 4; ++q) col[q] = 16 * q + 4 * g < U ? 4u * (16 * q + 4 * g) : kOutside;
     const float in_floor = act & ACT_RELU_IN ? 0.0f : -INFINITY;   // relu on the rows as they arrive, or nothing
-    float s_in = 1.0f, s_out = 1.0f;
-    if constexpr (SCALED) {
-        const float sm = (float)sums[2];
-        if (sm >= 1.0f && sm < 1e30f) {
-            int e;
-            (void)frexpf(sm, &e);          // sm = m 2^e, m in [0.5, 1)
-            s_in = ldexpf(1.0f, e - 1);
-            s_out = ldexpf(1.0f, 1 - e);
-        }
-    }
-    const float lo_unscale = QB_LO_UNSCALE * s_out;
     for (int64_t tile = (int64_t)blockIdx.x * 16 + wave; tile < ntile; tile += (int64_t)gridDim.x * 16) {
         const int64_t v = tile * 16 + i;
         const bool ok = v < N;
@@ -1004,6 +1022,9 @@ __global__ __launch_bounds__(1024) void conv9h_kernel(const float* __restrict__ 
             out[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             cross[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         }
+        float dscale = kDeltaScale0;   // SCALED: this voxel's delta scale, 2^dexp
+        int dexp = kDeltaScale0Exp;
+        float amax = 0.0f;             // !SCALED: the largest |operand| of the voxel's nine neighbour rows (NaN: NaN)
         // Rows come through a buffer resource of N x 256 bytes: a padded tap, a voxel beyond the batch or a
         // padding column reads at an offset outside it and the hardware returns zeros -- no selects behind the
         // loads.  The nine taps are unrolled with the next tap's four row quarters in flight during this tap's
@@ -1030,13 +1051,43 @@ __global__ __launch_bounds__(1024) void conv9h_kernel(const float* __restrict__ 
                 for (int q = 0; q < 4; ++q) rows[(tap + 1) & 1][q] = rows[tap & 1][q]; }
             if (!some[tap & 1]) continue;  // the whole tile reads padding
             const float4(&rw)[4] = rows[tap & 1];
+            if constexpr (SCALED) {
+                float dm = 0.0f;   // the largest |delta| of this lane's quarter of the row
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    amax_pair(dm, rw[q].x, rw[q].y);
+                    amax_pair(dm, rw[q].z, rw[q].w);
+                }
+                // the slow path only when some lane's deltas pass the trip (not for inf / NaN: they pass as they are):
+                // the voxel's four lanes agree on its largest |delta|, which lands in [2^11, 2^12)
+                if (__builtin_amdgcn_ballot_w64(!(dm * dscale < kDeltaTrip) && dm <= 3.0e38f) != 0) {
+                    dm = fmaxf(dm, __shfl_xor(dm, 16, 64));
+                    dm = fmaxf(dm, __shfl_xor(dm, 32, 64));
+                    if (!(dm * dscale < kDeltaTrip) && dm <= 3.0e38f) {
+                        int e;
+                        (void)frexpf(dm, &e);                        // dm = f 2^e, f in [0.5, 1)
+                        const float f = ldexpf(1.0f, 12 - e - dexp);  // new scale / old scale
+                        dexp = 12 - e;
+                        dscale = ldexpf(1.0f, dexp);
+#pragma unroll
+                        for (int m = 0; m < 4; ++m) {
+                            out[m] *= f;
+                            cross[m] *= f;
+                        }
+                    }
+                }
+            }
             qb::f16x8 bhi[2], blo[2];
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
                 float x8[8] = {rw[2 * st].x, rw[2 * st].y, rw[2 * st].z, rw[2 * st].w,
                                rw[2 * st + 1].x, rw[2 * st + 1].y, rw[2 * st + 1].z, rw[2 * st + 1].w};
 #pragma unroll
-                for (int j8 = 0; j8 < 8; ++j8) x8[j8] = SCALED ? x8[j8] * s_in : max_1op(x8[j8], in_floor);
+                for (int j8 = 0; j8 < 8; ++j8) x8[j8] = SCALED ? x8[j8] * dscale : max_keep_nan(x8[j8], in_floor);
+                if constexpr (!SCALED) {
+#pragma unroll
+                    for (int j8 = 0; j8 < 8; j8 += 2) amax_pair_nan(amax, x8[j8], x8[j8 + 1]);
+                }
                 if (QB_CONV9H_ABL & 8) {
                     bhi[st] = __builtin_bit_cast(qb::f16x8, rw[2 * st]);
                     blo[st] = __builtin_bit_cast(qb::f16x8, rw[2 * st + 1]);
@@ -1060,7 +1111,16 @@ __global__ __launch_bounds__(1024) void conv9h_kernel(const float* __restrict__ 
                 }
             }
         }
+        // forward: the operand range guard of encoder_core.h over the voxel's four lanes -- an operand beyond f16's
+        // range (or a NaN one) makes the voxel's output row NaN, never a clamped number
+        bool poison = false;
+        if constexpr (!SCALED) {
+            amax_pair_nan(amax, __shfl_xor(amax, 16, 64), amax);
+            amax_pair_nan(amax, __shfl_xor(amax, 32, 64), amax);
+            poison = qb::split_overflowed(amax);
+        }
         if (!ok) continue;
+        const float s_out = SCALED ? ldexpf(1.0f, -dexp) : 1.0f, lo_unscale = QB_LO_UNSCALE * s_out;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int j = 16 * m + 4 * g;
@@ -1072,6 +1132,7 @@ __global__ __launch_bounds__(1024) void conv9h_kernel(const float* __restrict__ 
                 yv[r] = SCALED ? fmaf(cross[m][r], lo_unscale, out[m][r] * s_out) + bj[r]
                                : fmaf(cross[m][r], QB_LO_UNSCALE, out[m][r]) + bj[r];
                 if (act & ACT_RELU) yv[r] = fmaxf(yv[r], 0.0f);
+                if (poison) yv[r] = __builtin_nanf("");
             }
             if (j + 3 < U) {
                 if (mask) {
@@ -1442,7 +1503,7 @@ __device__ __forceinline__ f32x4 bf3_mfma(const Bf3& x, const Bf3Cols& d, f32x4 
 // deltas are multiplied by s (a power of two) before the split and the wave's accumulators hold s x the sums.  A step
 // whose largest |delta| x s reaches 2^14 (one v_max3 per pair, one compare, one scalar branch) takes the slow path
 // once: the wave's maximum sets s so that it lands in [2^11, 2^12) and the accumulators are rescaled (exact).  s
-// starts at 2^60, so the first step with a delta above 1e-14 sets it; the expected number of later events is the
+// starts at 2^126 (kDeltaScale0), so the first step with a delta above 2^-112 sets it; the expected number of later events is the
 // number of record highs of a sequence, ~ ln(steps).  Smaller deltas that follow keep 2^-25 x 2^-12 of the
 // largest seen as their absolute error -- nothing in a sum the large ones dominate.  Activations are taken as they
 // are: the forward's own limit (|x| < 65504, include/qbold_hip.h) applies, beyond it the gradient is NaN, not a clamp.
@@ -1500,8 +1561,6 @@ template <> struct DwOps<true> {
     static __device__ __forceinline__ void cols(const float (&d)[4], float s, Cols& o) { h2_cols(d, s, o); }
     static __device__ __forceinline__ f32x4 mfma(const Rows& x, const Cols& d, f32x4 acc) { return h2_mfma(x, d, acc); }
 };
-constexpr float kDeltaScale0 = 1.152921504606846976e18f;   // 2^60
-constexpr float kDeltaTrip = 16384.0f;                      // 2^14: f16 ends at 65504
 // the slow path of the wave's delta scale: m = this lane's largest |delta| of the step; returns the factor the
 // accumulators take (new scale / old scale) and sets the new scale
 __device__ __forceinline__ float delta_rescale(float m, float& scale) {
@@ -2846,9 +2905,8 @@ struct Launcher {
     }
     // 3x3x1 'same' convolution as nine gathered GEMMs: Y = act(sum_taps X[nbr] K[tap] + b).
     // flip = 1 is the adjoint wrt the input (taps mirrored, kernels transposed).
-    // delta_sums (backward-data launches): the device double[3] whose [2] is the sum(mask) the deltas were divided by
     void conv3x3(const float* X, const float* K9, int U, const float* b, float* Y, int act, int flip,
-                 const float* mask, const qbold_geometry& gm, const double* delta_sums = nullptr) {
+                 const float* mask, const qbold_geometry& gm) {
         if (U <= 64 && ld == kLd && !(ctx->kernel_sel & 256)) {  // one launch, accumulators in registers
             const int64_t nb = (N + 255) / 256;
             const int64_t cap = (int64_t)ctx->num_cus;
@@ -2859,13 +2917,12 @@ struct Launcher {
                                    reinterpret_cast<uintptr_t>(mask)) & 15) == 0;
             if (aligned && U % 4 == 0 && N < (1 << 23) && !(ctx->kernel_sel & 65536) && !(act & (ACT_GELU | ACT_GELU_IN))) {   // split-f16 matrix pipe (bit 65536 / gelu / odd widths: the exact-f32 form)
                 const size_t smh = sizeof(float) * (9 * 4096 + 64);
-                const bool scaled = delta_sums && !(act & ACT_RELU_IN);
+                const bool scaled = flip && !(act & ACT_RELU_IN);   // backward-data: deltas under the running scale
                 auto kern = scaled ? conv9h_kernel<true> : conv9h_kernel<false>;
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smh);
                 hipLaunchKernelGGL(kern, dim3((unsigned)(nb < cap ? (nb > 0 ? nb : 1) : cap)), dim3(1024), smh, s,
-                                   X, ld, U, K9, flip, b, Y, ld, act, mask, ld, N, make_gather(gm.X, gm.Y, gm.Z, 0, 0),
-                                   delta_sums);
+                                   X, ld, U, K9, flip, b, Y, ld, act, mask, ld, N, make_gather(gm.X, gm.Y, gm.Z, 0, 0));
                 gather = make_gather(0, 0, 0, 0, 0);
                 return;
             }
@@ -3493,7 +3550,7 @@ static int train_bwd_gelu(const qbold_ctx* ctx, const qbold_encoder_shape* shape
             gelu_of(b_in, Gb);
             if (gm) {
                 k.xtd9(t, U, dD, partial, slabs9, gb + c.Wr2, gb + c.br2, *gm);
-                k.conv3x3(dD, wb + c.Wr2, U, nullptr, dE, ACT_NONE, 1, nullptr, *gm, sums);     // d t (post-activation)
+                k.conv3x3(dD, wb + c.Wr2, U, nullptr, dE, ACT_NONE, 1, nullptr, *gm);     // d t (post-activation)
                 k.conv3x3(Gb, wb + c.Wr1, U, wb + c.br1, Z, ACT_NONE, 0, nullptr, *gm);   // z_t, model.py:152
             } else {
                 k.xtd(t, U, dD, U, partial, slabs, gb + c.Wr2 + ctr, U, gb + c.br2, 0);
@@ -3503,7 +3560,7 @@ static int train_bwd_gelu(const qbold_ctx* ctx, const qbold_encoder_shape* shape
             times_dgelu(dE, Z);                                                           // d z_t
             if (gm) {
                 k.xtd9(Gb, U, dE, partial, slabs9, gb + c.Wr1, gb + c.br1, *gm, 0);
-                k.conv3x3(dE, wb + c.Wr1, U, nullptr, dB, ACT_NONE, 1, nullptr, *gm, sums);     // d gelu(b_in)
+                k.conv3x3(dE, wb + c.Wr1, U, nullptr, dB, ACT_NONE, 1, nullptr, *gm);     // d gelu(b_in)
             } else {
                 k.xtd(Gb, U, dE, U, partial, slabs, gb + c.Wr1 + ctr, U, gb + c.br1, 0, 0);
                 k.xw(dE, ld, U, wb + c.Wr1 + ctr, U, 1, nullptr, dB, U, ACT_NONE, 0, nullptr);
@@ -3614,7 +3671,7 @@ static int train_bwd_norm(const qbold_ctx* ctx, const qbold_encoder_shape* shape
         normalizer(p, 1, Z);                                                          // a2 (and p's statistics)
         if (gm) {
             k.xtd9(Z, U, dD, partial, slabs9, gb + c.Wr2, gb + c.br2, *gm);
-            k.conv3x3(dD, wb + c.Wr2, U, nullptr, dE, ACT_NONE, 1, nullptr, *gm, sums);     // d a2
+            k.conv3x3(dD, wb + c.Wr2, U, nullptr, dE, ACT_NONE, 1, nullptr, *gm);     // d a2
         } else {
             k.xtd(Z, U, dD, U, partial, slabs, gb + c.Wr2 + ctr, U, gb + c.br2, 0);
             k.xw(dD, ld, U, wb + c.Wr2 + ctr, U, 1, nullptr, dE, U, ACT_NONE, 0, nullptr);
@@ -3625,7 +3682,7 @@ static int train_bwd_norm(const qbold_ctx* ctx, const qbold_encoder_shape* shape
         normalizer(b_in, 0, A1);
         if (gm) {
             k.xtd9(A1, U, dE, partial, slabs9, gb + c.Wr1, gb + c.br1, *gm, 0);
-            k.conv3x3(dE, wb + c.Wr1, U, nullptr, dB, ACT_NONE, 1, nullptr, *gm, sums);     // d a1
+            k.conv3x3(dE, wb + c.Wr1, U, nullptr, dB, ACT_NONE, 1, nullptr, *gm);     // d a1
         } else {
             k.xtd(A1, U, dE, U, partial, slabs, gb + c.Wr1 + ctr, U, gb + c.br1, 0, 0);
             k.xw(dE, ld, U, wb + c.Wr1 + ctr, U, 1, nullptr, dB, U, ACT_NONE, 0, nullptr);
@@ -3833,10 +3890,10 @@ static int train_bwd_impl(const qbold_ctx* ctx, const qbold_encoder_shape* shape
             if (gm) {
                 // second residual conv (3x3x1): dK2[tap] = t[nbr]^T dD; d t_pre = conv^T(dD) * (t > 0) -> dE
                 k.xtd9(t, U, dD, partial, slabs9, gb + c.Wr2, gb + c.br2, *gm);
-                k.conv3x3(dD, wb + c.Wr2, U, nullptr, dE, ACT_NONE, 1, t, *gm, sums);
+                k.conv3x3(dD, wb + c.Wr2, U, nullptr, dE, ACT_NONE, 1, t, *gm);
                 // first residual conv: input relu(b_in)
                 k.xtd9(b_in, U, dE, partial, slabs9, gb + c.Wr1, gb + c.br1, *gm, 1);
-                k.conv3x3(dE, wb + c.Wr1, U, nullptr, dB, ACT_NONE, 1, b_in, *gm, sums);
+                k.conv3x3(dE, wb + c.Wr1, U, nullptr, dB, ACT_NONE, 1, b_in, *gm);
             } else {
                 const int ctr = c.taps == 9 ? 4 * U * U : 0;
                 // second residual conv: dWr2 = t^T dD; d t_pre = (dD Wr2^T) * (t > 0)  -> dE
