@@ -346,18 +346,56 @@ __device__ __forceinline__ void dense_first(const float* __restrict__ A,
     for (int m = 0; m < 4; ++m) out[m] = relu4(out[m]);
 }
 
+// The B fragments of relu(x) from those of x, on the packed halves: hi' = max(hi, 0), and lo' = lo where hi's sign
+// bit is clear, +0 where it is set.  Bit for bit split_act(relu4(x)): hi = f16(x) carries x's sign (x < 0 rounds to
+// a negative half or to -0, whose sign bit clears lo; v_pk_max_f16 orders -0 below +0 and returns +0, and
+// relu4(-0) splits to +0, +0 as well), and for x >= 0 nothing changes.  Three packed instructions per register pair
+// of halves (24 per tensor) where relu4 + split_act issue 48.  A NaN input is the one case that differs (relu4 gives 0,
+// here lo may stay NaN): it only follows an operand overflow, which amax has already caught and the voxel is poisoned.
+// tests/test_gpu_relu_frag.py compares the bits of both forms on the edge values.
+__device__ __forceinline__ ActFrag relu_frag(const ActFrag& f) {
+    typedef uint32_t u32x4r __attribute__((ext_vector_type(4)));
+    ActFrag o;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const u32x4r h = __builtin_bit_cast(u32x4r, f.hi[s]), l = __builtin_bit_cast(u32x4r, f.lo[s]);
+        u32x4r hp, lp;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            uint32_t neg;   // 0xffff per negative half (written on vectors of short the compiler goes through compares and selects)
+            asm("v_pk_max_f16 %0, %1, 0" : "=v"(hp[p]) : "v"(h[p]));
+            asm("v_pk_ashrrev_i16 %0, 15, %1 op_sel_hi:[0,1]" : "=v"(neg) : "v"(h[p]));
+            lp[p] = l[p] & ~neg;
+        }
+        o.hi[s] = __builtin_bit_cast(f16x8, hp);
+        o.lo[s] = __builtin_bit_cast(f16x8, lp);
+    }
+    return o;
+}
+
 // One create_block step of stream 2 (gated residual), in place -- model.py:147-172.
-template <bool BF = false>
+// NONNEG: every b[m][k] is >= 0 on entry (block 0: dense_first ends in relu4), so the activation before the first
+// 3x3x1 conv is the identity and that conv takes the very fragments the shared conv just used.  Otherwise the
+// split-f16 path derives relu(b)'s fragments from b's (relu_frag); bf16 fragments are split again from relu4(b).
+template <bool BF = false, bool NONNEG = false>
 __device__ __forceinline__ void block_stream2(const float* __restrict__ W, f32x4 (&b)[4],
                                               int lane, float* amax = nullptr) {
     f32x4 skip[4], t[4], r[4];
-    dense64<BF>(W + BLK_WC_A, W + BLK_WC_B, b, skip, lane, amax);  // shared 1x1x1 conv as skip, :148
+    const ActFrag fb = split_act<BF>(b, amax);
+    dense_f16x3<4, 2, BF>(W + BLK_WC_A, W + BLK_WC_B, fb.hi, fb.lo, skip, lane);  // shared 1x1x1 conv as skip, :148
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        skip[m] = relu4(skip[m]);
-        b[m] = relu4(b[m]);  // Activation before the first 3x3x1 conv, :151
+    for (int m = 0; m < 4; ++m) skip[m] = relu4(skip[m]);
+    // Activation before the first 3x3x1 conv, :151, then the conv, :152  (|relu b| <= |b|: already tracked)
+    if constexpr (NONNEG) {
+        dense_f16x3<4, 2, BF>(W + BLK_R1_A, W + BLK_R1_B, fb.hi, fb.lo, t, lane);
+    } else if constexpr (!BF) {
+        const ActFrag fr = relu_frag(fb);
+        dense_f16x3<4, 2, BF>(W + BLK_R1_A, W + BLK_R1_B, fr.hi, fr.lo, t, lane);
+    } else {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) b[m] = relu4(b[m]);
+        dense64<BF>(W + BLK_R1_A, W + BLK_R1_B, b, t, lane);
     }
-    dense64<BF>(W + BLK_R1_A, W + BLK_R1_B, b, t, lane);  // :152  (|relu b| <= |b|: already tracked)
 #pragma unroll
     for (int m = 0; m < 4; ++m) t[m] = relu4(t[m]);   // :155
     dense64<BF>(W + BLK_R2_A, W + BLK_R2_B, t, r, lane, amax);  // :156

@@ -140,8 +140,9 @@ __global__ __launch_bounds__(kEncBlock) void encoder_fwd_kernel(
         if (out2 || sigma) {
             f32x4 b[4] = {a[0], a[1], a[2], a[3]};  // net2 = net1, model.py:185
             float amax = lds_w[e.flag];   // 0, or the largest unsplittable weight
+            qb::block_stream2<BF, true>(lds_w + e.blk0, b, lane, &amax);   // b = relu4(.) >= 0 out of dense_first
 #pragma unroll
-            for (int l = 0; l < NL; ++l) qb::block_stream2<BF>(lds_w + e.blk0 + l * e.blk_stride, b, lane, &amax);
+            for (int l = 1; l < NL; ++l) qb::block_stream2<BF>(lds_w + e.blk0 + l * e.blk_stride, b, lane, &amax);
             f32x4 hd[HT];
             qb::dense_head<HT, BF>(lds_w + e.head_A, lds_w + e.head_b, b, hd, lane, &amax);
             float o[5 + T];

@@ -132,9 +132,12 @@ __global__ __launch_bounds__(BLK) void vi_fwd_kernel(
             __builtin_amdgcn_s_setprio(2);
             f32x4 b[4];
             qb::dense_first<T, BF>(lds_w + e.first_A, lds_w + e.first_b, nv, b, lane);
-            if (!QB_ABLATE(c, 1) && qb_phase_fence())
+            if (!QB_ABLATE(c, 1) && qb_phase_fence()) {
+                // block 0 reads dense_first's output, which its relu4 left non-negative
+                qb::block_stream2<BF, true>(lds_w + e.blk0, b, lane, &amax);
 #pragma unroll
-                for (int l = 0; l < NL; ++l) qb::block_stream2<BF>(lds_w + e.blk0 + l * e.blk_stride, b, lane, &amax);
+                for (int l = 1; l < NL; ++l) qb::block_stream2<BF>(lds_w + e.blk0 + l * e.blk_stride, b, lane, &amax);
+            }
             f32x4 hd[HT];
             qb::dense_head<HT, BF>(lds_w + e.head_A, lds_w + e.head_b, b, hd, lane, &amax);
             qb::gather_head<5 + T, HT>(hd, o);
