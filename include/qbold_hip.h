@@ -169,7 +169,8 @@ int qbold_ctx_set_grad_node0(qbold_ctx* ctx, int on);
 #define QBOLD_KSEL_HEADS_BWD_LAYERWISE 1048576 /* heads' backward as delta tensor + GEMM + weight-gradient pass */
 #define QBOLD_KSEL_SLAB_SUMS_SEPARATE 2097152 /* crop backward: every weight-gradient slab sum as its own launch instead of the queued ones */
 #define QBOLD_KSEL_DW_BF16_PIECES 4194304     /* layer-wise weight gradients on three bfloat16 pieces per operand instead of two f16 halves */
-#define QBOLD_KSEL_ALL (4 | 8 | 256 | 512 | 2048 | 4096 | 8192 | 16384 | 32768 | 65536 | 131072 | 262144 | 524288 | 1048576 | 2097152 | 4194304)
+#define QBOLD_KSEL_ELBO_BWD_GENERIC 8388608   /* qbold_elbo_bwd at T = 11 / 24: the run-time-T kernel of every other protocol (Gaussian likelihood on linear data; Student-t / log-data contexts keep the specialised kernels) */
+#define QBOLD_KSEL_ALL (4 | 8 | 256 | 512 | 2048 | 4096 | 8192 | 16384 | 32768 | 65536 | 131072 | 262144 | 524288 | 1048576 | 2097152 | 4194304 | 8388608)
 int qbold_ctx_set_kernel_selection(qbold_ctx* ctx, int mask);
 /* Host-side evaluation of the uploaded table (for tests): F(x) and dF/dx, HOST arrays. */
 int qbold_ctx_table_eval(const qbold_ctx* ctx, const float* host_x, float* host_F, float* host_dF,
@@ -399,7 +400,7 @@ int qbold_log_evidence_fwd(const qbold_ctx* ctx, const float* x, const float* ma
  *     normaliser qbold_encoder_train_bwd / qbold_encoder_spatial_bwd read
  *   workspace: qbold_elbo_workspace_bytes() bytes.
  * Fixed-order sums, no atomics: a voxel's outputs are the same bits at any batch position, under any sharding by voxel0
- * and run to run.  Configurations of qbold_elbo_bwd (full model, table mode, T = 11 or 24), the use_mvg = True family;
+ * and run to run.  Full signal model in table mode, T = 11 or 24 (qbold_elbo_bwd's other protocols are not built here), the use_mvg = True family;
  * QBOLD_ERR_UNSUPPORTED otherwise.  QBOLD_ERR_INVALID for K < 1, K > QBOLD_IW_MAX_K or a NULL required buffer. */
 int qbold_log_evidence_bwd(const qbold_ctx* ctx, const float* x, const float* mask, const float* q,
                            const float* prior, const float* log_sigma, const float* z, int K, uint64_t seed,
@@ -422,7 +423,7 @@ int qbold_log_evidence_bwd(const qbold_ctx* ctx, const float* x, const float* ma
  *     steps Sp), so results do not depend on the sharding.
  *   loss [N][2] or NULL: the Monte-Carlo -ELBO (mean NLL of the step's draws + closed-form KL) at step 0 and its mean
  *     over the last ceil(steps / 10) steps; 0 for masked voxels.
- * Full signal model in table mode, T = 11 or 24 (qbold_elbo_bwd's configurations); QBOLD_ERR_UNSUPPORTED otherwise.
+ * Full signal model in table mode, T = 11 or 24; QBOLD_ERR_UNSUPPORTED otherwise.
  * QBOLD_ERR_INVALID for steps < 1, S < 1, steps Sp / 4 >= 2^32 (the Philox call word), lr <= 0, lr_final < 0, Adam
  * betas outside [0, 1) or eps <= 0, an optimizer other than 0 / 1, or a NULL required buffer. */
 typedef struct {
@@ -548,8 +549,12 @@ int qbold_posterior_predictive(const qbold_ctx* ctx, const float* x, const float
  *   g_q [N][5], g_log_sigma [N][T]:  m_v * d nll_v/d. + [m_v > 0] * d kl_v/d.   (NOT divided by
  *   sum(m): the caller scales the weight gradient once)
  *   nll_kl, sums, workspace: as qbold_elbo_fwd (same Philox stream -> same loss values).
- * Built for the full signal model in table mode; Gaussian or Student-t likelihood, linear or log
- * data, one- or three-image normalisation (the switches of qbold_loss_cfg). */
+ * Built for the full signal model in table mode.  T = 11 or 24: Gaussian or Student-t likelihood, linear or log
+ * data, one- or three-image normalisation (the switches of qbold_loss_cfg).  Every other 1 <= T <= 64, with or
+ * without a tau equal to 0: the configurations qbold_elbo_fwd runs there (Gaussian likelihood on linear data, one-
+ * or three-image normalisation, any spin-echo index), same Philox words and the same fixed-order sums, so the
+ * outputs are the same bits under any sharding by voxel0 and run to run; Student-t or log data at such a T return
+ * QBOLD_ERR_UNSUPPORTED.  QBOLD_KSEL_ELBO_BWD_GENERIC runs T = 11 / 24 on that kernel too. */
 int qbold_elbo_bwd(const qbold_ctx* ctx, const float* x, const float* mask, const float* q,
                    const float* prior, const float* log_sigma, int S, int K, uint64_t seed,
                    int64_t voxel0, float* g_q, float* g_log_sigma, float* nll_kl, double* sums,

@@ -313,6 +313,310 @@ __global__ __launch_bounds__(kBlock) void elbo_bwd_kernel(
     qb::block_partials(red, s_nll, s_kl, s_m, partials);
 }
 
+// ---- any number of taus (1 <= T <= QB_MAX_T) ------------------------------------------------------------------------
+// The same function as elbo_bwd_kernel with T and the spin-echo index read at run time, for elbo_fast_path
+// configurations (full model, table mode, Gaussian likelihood, linear data; either normalisation; no tau needs to be 0:
+// nothing here uses the protocol's mirror symmetry).  Same Philox words, same draw-to-lane dealing for either LPV, and
+// for the VALUE the same arithmetic in the same order as elbo_bwd_kernel (fwd_signal_fast's signal, the ascending-t
+// residual sum, the five-moment KL), so nll / kl come out as that kernel's; the gradients are regrouped (below) and
+// differ from it by rounding.
+//
+// Traffic per voxel, read from the code: reads 4T (x) + 4T (log sigma) + 20 (q) + 20 (prior) + 4 (mask), writes
+// 4T (g_log_sigma) + 20 (g_q) + 8 (nll_kl): 12T + 72 B, 840 B at T = 64, each row touched once per lane that owns the
+// voxel (LPV = 4: the four lanes repeat the reads, as in elbo_bwd_kernel).  VALU-bound like its neighbours.
+//
+// What elbo_bwd_kernel keeps as register arrays lives in dynamic LDS, as rows [t][thread] of kGenBlock floats beside
+// FwdLds: the normalised data yt, 1 / sigma, and (LPV = 4) the lane's g_log_sigma accumulators -- 12 T bytes per
+// thread (T = 11: 16.5 KiB per block, T = 64: 96 KiB, one block per CU).  With one lane per voxel (S <= 2) the lane
+// is the only writer of its voxel's g_log_sigma row, so the sums go straight to global memory -- a store per tau on
+// the first draw, a read-add-store on the second -- and the third row is not allocated: 8 T bytes per thread, two
+// blocks (one wave per SIMD) per CU at T = 64.  A thread owns its column of every row, so a wave's access at a
+// fixed t is 64 consecutive floats (conflict-free on the 64 banks) and no barrier is needed after the table fill.  sig[t] and gy[t] of the specialised kernel's two passes are not kept
+// at all: with gy_t = d nll / d yhat_t the chain through yhat_t = sig_t / np is
+//     g_oef = sum_t (gy_t / np - [t in norm window] w a1) ds_t/doef = (1/np) sum_t gy_t ds_t/doef - w a1 sum_window ds_t/doef,
+//     a1 = (1/np^2) sum_t gy_t sig_t,  w = 1 or 1/3,
+// so ONE pass over t gathers sum gy sig, sum gy ds/doef, sum gy ds/ddbv and the window's slopes, after the one or
+// three signal evaluations that give np.  That is T + 1 (T + 3) table lookups per draw where two passes take 2 T.
+constexpr int kGenBlock = 128;
+constexpr int gen_rows(int lpv) { return lpv == 1 ? 2 : 3; }
+static_assert(sizeof(qb::FwdLds) + sizeof(float) * gen_rows(QB_LANES_PER_VOXEL) * QB_MAX_T * kGenBlock <= 160 * 1024,
+              "elbo_bwd_generic_kernel: table + rows exceed the LDS");
+
+struct GenSig {
+    float s, F, e1, e2, u, f, B;
+    float4 k;
+};
+// fwd_signal_fast, keeping what the slopes need; blood_B from LDS (t is a run-time index here)
+__device__ __forceinline__ GenSig gen_signal(const qb::FwdLds* L, const qb::FwdFast& v, int t) {
+    GenSig g;
+    g.u = fabsf(fmaf((float)t, v.ub, v.ua));
+    const int i = (int)g.u;
+    g.f = __builtin_amdgcn_fractf(g.u);
+    g.k = L->tab[i];
+    g.F = fmaf(fmaf(fmaf(g.k.w, g.f, g.k.z), g.f, g.k.y), g.f, g.k.x);
+    g.e1 = qb::exp2f_(v.nd * g.F);
+    g.B = L->blood_B[t];
+    g.e2 = qb::exp2f_(v.ng * g.B);
+    g.s = fmaf(v.tissue_w, g.e1, v.blood_w * g.e2);
+    return g;
+}
+
+template <int LPV>
+__global__ __launch_bounds__(kGenBlock) void elbo_bwd_generic_kernel(
+    QbDev c, const float4* __restrict__ g_tab, const float* __restrict__ x,
+    const float* __restrict__ mask, const float* __restrict__ q, const float* __restrict__ prior,
+    const float* __restrict__ log_sigma, int S, int K, int kl_per_wave, uint64_t seed, int64_t voxel0,
+    float* __restrict__ g_q, float* __restrict__ g_ls, float2* __restrict__ nll_kl,
+    double* __restrict__ partials, int64_t N) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    qb::FwdLds* L = reinterpret_cast<qb::FwdLds*>(smem);
+    __shared__ double red[3 * (kGenBlock / 64)];
+    const int T = c.T, se = c.se_idx;
+    // this thread's column of the rows (gl: LPV > 1 only)
+    float* yt = reinterpret_cast<float*>(smem + sizeof(qb::FwdLds)) + threadIdx.x;
+    float* is = yt + T * kGenBlock;
+    float* gl = is + T * kGenBlock;
+    qb::fwd_lds_fill(L, g_tab, false);
+    if (threadIdx.x < QB_MAX_T) L->blood_B[threadIdx.x] = c.blood_B[threadIdx.x];
+    __syncthreads();
+
+    constexpr int kVoxPerBlock = kGenBlock / LPV, kVoxPerWave = 64 / LPV;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int part = LPV == 1 ? 0 : lane >> 4;
+    auto voxel_sum = [](float x) { return LPV == 1 ? x : qb::voxel_sum(x); };
+    // normalisation window (model.py:541-545) and the weight of each of its images
+    const int w_lo = c.multi_norm ? se - 1 : se, w_hi = c.multi_norm ? se + 1 : se;
+    const float w_se = c.multi_norm ? 1.0f / 3.0f : 1.0f;
+    const float dbw = c.include_blood ? c.m_bld_nb : 1.0f;
+    const float n0 = c.dF_node0 / (c.tab_inv_h * c.tab_inv_h);   // node 0's slope per u^2
+    float s_nll = 0.0f, s_kl = 0.0f, s_m = 0.0f;
+    const int64_t ntile = (N + kVoxPerBlock - 1) / kVoxPerBlock;
+    for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+        const int64_t v = tile * kVoxPerBlock + wave * kVoxPerWave + (LPV == 1 ? lane : lane & 15);
+        if (v < N) {
+            const float* xv = x + v * T;
+            const float* lv = log_sigma + v * T;
+            float qv[5], pv[5];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                qv[i] = q[v * 5 + i];
+                pv[i] = prior[v * 5 + i];
+            }
+            const float m = mask ? mask[v] : 1.0f;
+            // prepare_lik<T, SE, true>: se_norm on the data, yt = x / norm, 1 / sigma = exp(-log sigma)
+            const float nt = c.multi_norm ? (xv[se - 1] + xv[se] + xv[se + 1]) / 3.0f + 1e-3f : xv[se] + 1e-3f;
+            const float inv_nt = qb::rcpf_(nt);
+            float ls = 0.0f;
+            for (int t = 0; t < T; ++t) {
+                const float l = lv[t];
+                yt[t * kGenBlock] = xv[t] * inv_nt;
+                is[t * kGenBlock] = qb::exp2f_(-QB_LOG2E * l);
+                if (LPV > 1) gl[t * kGenBlock] = 0.0f;
+                ls += l;
+            }
+            const float log_s_sum = ls + (float)T * 0.9189385332046727f;  // log sqrt(2 pi)
+            const qb::LogitMvn qm = qb::make_mvn(qv), pm = qb::make_mvn(pv);
+            const uint64_t vox = (uint64_t)(voxel0 + v);
+            const float inv_S = 1.0f / (float)S;
+            const float wn = m * inv_S;  // weight of one likelihood draw in m_v * nll_v
+            float* gv = g_ls + v * T;
+
+            float g_mu_o = 0.0f, g_so = 0.0f, g_mu_d = 0.0f, g_sd = 0.0f, g_c = 0.0f;
+            float nll_sum = 0.0f, kl_sum = 0.0f;
+            int n_lik = 0, n_kl = 0;
+
+            // ---- likelihood draws --------------------------------------------------------
+            for (int g = part; 4 * g < S; g += LPV) {
+                const int cnt = S - 4 * g < 4 ? S - 4 * g : 4;
+                n_lik += cnt;
+                qb::DrawQuad dq;
+                dq.load(seed, vox, (uint32_t)g, qb::STREAM_LIK);
+#pragma unroll 1
+                for (int d = 0; d < cnt; ++d) {
+                    float z0, z1;
+                    dq.next(z0, z1);
+                    float a, b;
+                    qb::reparam_logits(qm, z0, z1, a, b);
+                    const float sa = qb::sigmoidf_(a), sb = qb::sigmoidf_(b);
+                    const float oef = sa * QB_OEF_RANGE + QB_MIN_OEF;
+                    const float dbv = sb * QB_DBV_RANGE + QB_MIN_DBV;
+                    const qb::FwdFast fv = qb::fwd_fast(c, oef, dbv);
+                    const float inv_oef = qb::rcpf_(oef);
+                    // se_norm on the prediction
+                    float np_ = gen_signal(L, fv, se).s;
+                    if (c.multi_norm) np_ = (gen_signal(L, fv, se - 1).s + np_ + gen_signal(L, fv, se + 1).s) / 3.0f;
+                    const float inv_np = qb::rcpf_(np_ + 1e-3f);
+                    // per-draw factors of the slopes (fwd_signal_grad): tissue exp(-dbv F(x)), x proportional to oef;
+                    // blood exp(-g B), g proportional to oef^2
+                    const float ko = -dbv * inv_oef, kb = (2.0f * QB_LN2) * fv.ng * inv_oef;
+                    const float kd1 = dbw * c.e_te_r2t, kd2 = c.include_blood ? dbw * c.e_r2b_te : 0.0f;
+                    float acc = 0.0f, a1 = 0.0f, go = 0.0f, gd = 0.0f, wo = 0.0f, wd = 0.0f;
+                    for (int t = 0; t < T; ++t) {
+                        const GenSig sg = gen_signal(L, fv, t);
+                        const float inv_s = is[t * kGenBlock];
+                        float r;
+                        {   // yhat rounded on its own, as in elbo_bwd_kernel (whose log-data select keeps the product
+                            // and the subtraction apart): the value stays that kernel's bit for bit
+#pragma clang fp contract(off)
+                            const float yp = sg.s * inv_np;
+                            r = (yt[t * kGenBlock] - yp) * inv_s;
+                        }
+                        acc = fmaf(r, r, acc);
+                        const float dls = 1.0f - r * r;           // d/d log sigma_t of log sigma_t + r^2 / 2
+                        if (LPV > 1) gl[t * kGenBlock] += dls;
+                        else if (g == 0 && d == 0) gv[t] = dls * wn;   // the voxel's first draw (the lane walks them in order)
+                        else gv[t] = fmaf(dls, wn, gv[t]);
+                        const float gy = -r * inv_s;              // d nll / d yhat_t
+                        a1 = fmaf(gy, sg.s, a1);
+                        // |x| dF/dx at x = u / tab_inv_h (the cubic's slope in u, plus node 0's slope in x): d|x|/doef = |x| / oef
+                        const float dFu = fmaf(fmaf(3.0f * sg.k.w, sg.f, 2.0f * sg.k.z), sg.f, sg.k.y) * sg.u + n0 * sg.u * sg.u;
+                        const float tissue = fv.tissue_w * sg.e1, blood = fv.blood_w * sg.e2;
+                        const float ds_doef = fmaf(ko * dFu, tissue, kb * sg.B * blood);
+                        const float ds_ddbv = fmaf(kd2, sg.e2, -fmaf(sg.F, tissue, kd1 * sg.e1));
+                        go = fmaf(gy, ds_doef, go);
+                        gd = fmaf(gy, ds_ddbv, gd);
+                        if (t >= w_lo && t <= w_hi) {             // wave-uniform
+                            wo += ds_doef;
+                            wd += ds_ddbv;
+                        }
+                    }
+                    nll_sum += acc;
+                    a1 *= inv_np * inv_np * w_se;                 // yhat_t = sig_t / (norm + 1e-3)
+                    const float g_oef = fmaf(go, inv_np, -a1 * wo), g_dbv = fmaf(gd, inv_np, -a1 * wd);
+                    const float ga = g_oef * QB_OEF_RANGE * sa * (1.0f - sa);  // forward_transform
+                    const float gb = g_dbv * QB_DBV_RANGE * sb * (1.0f - sb);
+                    g_mu_o += ga;
+                    g_so = fmaf(ga, z0 * qm.e_so, g_so);
+                    g_mu_d += gb;
+                    g_c = fmaf(gb, z0, g_c);
+                    g_sd = fmaf(gb, z1 * qm.e_sd, g_sd);
+                }
+            }
+            g_mu_o *= wn; g_so *= wn; g_mu_d *= wn; g_sd *= wn; g_c *= wn;
+            nll_sum = fmaf(0.5f, nll_sum, (float)n_lik * log_s_sum);
+
+            // ---- KL draws: elbo_bwd_kernel's two forms, statement for statement (that kernel's text is frozen with its
+            // bits, so the block is repeated here instead of shared) -------------------------
+            float k_mu_o = 0.0f, k_so = 0.0f, k_mu_d = 0.0f, k_sd = 0.0f, k_c = 0.0f;
+            constexpr float kZMax = QB_Z_MAX;
+            const float reach = fmaxf(fabsf(qm.mu_o) + kZMax * qm.e_so, fabsf(qm.mu_d) + kZMax * (fabsf(qm.c) + qm.e_sd));
+            // Which form a voxel takes is its own affair (its four lanes share q, so they agree): a voxel's outputs then
+            // do not depend on which voxels share its wave, i.e. on the batch position or the sharding, and a wave runs
+            // the general loop only for the lanes that need it.  elbo_bwd_kernel sends the whole wave through the
+            // general loop as soon as one of its voxels is over the bound; kl_per_wave (T = 11 / 24 under
+            // QBOLD_KSEL_ELBO_BWD_GENERIC, where this kernel stands in for that one) repeats that choice.
+            const bool fits = reach < QB_LOGIT_CLIP, wave_fits = __all(fits);
+            if (QB_BWD_WHITENED && (kl_per_wave ? wave_fits : fits)) {
+                float s0 = 0.0f, s1 = 0.0f, s00 = 0.0f, s11 = 0.0f, s01 = 0.0f;
+                for (int g = part; 4 * g < K; g += LPV) {
+                    float z[8];
+                    const int cnt = K - 4 * g < 4 ? K - 4 * g : 4;
+                    qb::normals8_unscaled(seed, vox, (uint32_t)g, qb::STREAM_KL, cnt, z);   // beyond K: z = 0
+                    n_kl += cnt;
+#pragma unroll
+                    for (int d = 0; d < 4; ++d) {
+                        const float z0 = z[2 * d], z1 = z[2 * d + 1];
+                        s0 += z0;
+                        s1 += z1;
+                        s00 = fmaf(z0, z0, s00);
+                        s11 = fmaf(z1, z1, s11);
+                        s01 = fmaf(z0, z1, s01);
+                    }
+                }
+                s0 *= QB_BM_K;
+                s1 *= QB_BM_K;
+                s00 *= QB_BM_K * QB_BM_K;
+                s11 *= QB_BM_K * QB_BM_K;
+                s01 *= QB_BM_K * QB_BM_K;
+                const float nk = (float)n_kl;
+                const float dmu_o = qm.mu_o - pm.mu_o, dmu_d = qm.mu_d - pm.mu_d;
+                const float d0 = dmu_o * pm.i_so, m00 = qm.e_so * pm.i_so;
+                const float d1 = fmaf(dmu_d, pm.i_sd, dmu_o * pm.i_bl);
+                const float m10 = fmaf(qm.c, pm.i_sd, qm.e_so * pm.i_bl), m11 = qm.e_sd * pm.i_sd;
+                const float sw0 = nk * d0 * d0 + 2.0f * d0 * m00 * s0 + m00 * m00 * s00;
+                const float sw1 = nk * d1 * d1 + 2.0f * d1 * (m10 * s0 + m11 * s1) + m10 * m10 * s00 +
+                                  2.0f * m10 * m11 * s01 + m11 * m11 * s11;
+                kl_sum = (sw0 + sw1) - (s00 + s11);
+                const float A0 = d0 * pm.i_so + d1 * pm.i_bl;
+                const float A1 = m00 * pm.i_so + m10 * pm.i_bl - qm.i_so;
+                const float A2 = m11 * pm.i_bl - qm.i_bl;
+                const float B0 = d1 * pm.i_sd, B1 = m10 * pm.i_sd, B2 = m11 * pm.i_sd - qm.i_sd;
+                k_mu_o = A0 * nk + A1 * s0 + A2 * s1;
+                k_so = (A0 * s0 + A1 * s00 + A2 * s01) * qm.e_so;
+                k_mu_d = B0 * nk + B1 * s0 + B2 * s1;
+                k_c = B0 * s0 + B1 * s00 + B2 * s01;
+                k_sd = (B0 * s1 + B1 * s01 + B2 * s11) * qm.e_sd;
+            } else
+            for (int g = part; 4 * g < K; g += LPV) {
+                const int cnt = K - 4 * g < 4 ? K - 4 * g : 4;
+                n_kl += cnt;
+                qb::DrawQuad dq;
+                dq.load(seed, vox, (uint32_t)g, qb::STREAM_KL);
+#pragma unroll 1
+                for (int d = 0; d < cnt; ++d) {
+                    float z0, z1;
+                    dq.next(z0, z1);
+                    float a, b;
+                    qb::reparam_logits(qm, z0, z1, a, b);
+                    const float l0 = qb::clampf_(a, -QB_LOGIT_CLIP, QB_LOGIT_CLIP);
+                    const float l1 = qb::clampf_(b, -QB_LOGIT_CLIP, QB_LOGIT_CLIP);
+                    const float rq0 = l0 - qm.mu_o, rq1 = l1 - qm.mu_d;
+                    const float rp0 = l0 - pm.mu_o, rp1 = l1 - pm.mu_d;
+                    const float wq0 = rq0 * qm.i_so, wq1 = fmaf(rq1, qm.i_sd, rq0 * qm.i_bl);
+                    const float wp0 = rp0 * pm.i_so, wp1 = fmaf(rp1, pm.i_sd, rp0 * pm.i_bl);
+                    kl_sum += fmaf(wp0, wp0, wp1 * wp1) - fmaf(wq0, wq0, wq1 * wq1);
+                    // the clip passes gradient (tfp clip_by_value_preserve_gradient, model.py:395)
+                    const float ga = (wp0 * pm.i_so + wp1 * pm.i_bl) - (wq0 * qm.i_so + wq1 * qm.i_bl);
+                    const float gb = wp1 * pm.i_sd - wq1 * qm.i_sd;
+                    k_mu_o += ga;
+                    k_so = fmaf(ga, z0 * qm.e_so, k_so);
+                    k_mu_d += gb;
+                    k_c = fmaf(gb, z0, k_c);
+                    k_sd = fmaf(gb, z1 * qm.e_sd, k_sd);
+                }
+            }
+            kl_sum = fmaf(0.5f, kl_sum, (float)n_kl * ((pm.s_o + pm.s_d) - (qm.s_o + qm.s_d)));
+            if (K > 0) {
+                const float wk = (m > 0.0f ? 1.0f : 0.0f) / (float)K;
+                g_mu_o = fmaf(wk, k_mu_o, g_mu_o);
+                g_so = fmaf(wk, k_so, g_so);
+                g_mu_d = fmaf(wk, k_mu_d, g_mu_d);
+                g_sd = fmaf(wk, k_sd, g_sd);
+                g_c = fmaf(wk, k_c, g_c);
+            }
+            // combine the lanes of the voxel (all LPV of them are active together: v depends on lane & 15 only)
+            g_mu_o = voxel_sum(g_mu_o);
+            g_so = voxel_sum(g_so);
+            g_mu_d = voxel_sum(g_mu_d);
+            g_sd = voxel_sum(g_sd);
+            g_c = voxel_sum(g_c);
+            if (LPV > 1) {
+                for (int t = 0; t < T; ++t) {
+                    const float gt = voxel_sum(gl[t * kGenBlock] * wn);
+                    if ((t & (LPV - 1)) == part) gv[t] = gt;   // the voxel's lanes share the stores
+                }
+            }
+            const float nll = voxel_sum(nll_sum) * inv_S;
+            const float kl = K > 0 ? voxel_sum(kl_sum) / (float)K : 0.0f;
+            if (part == 0) {
+                // transform_std / transform_offdiag (model.py:288-294), as in elbo_bwd_kernel
+                const float th1 = (qm.s_o + 1.0f) * (1.0f / 3.0f), th3 = (qm.s_d + 1.0f) * (1.0f / 3.0f);
+                const float th4 = qm.c * 7.38905609893065f;
+                g_q[v * 5 + 0] = g_mu_o;
+                g_q[v * 5 + 1] = g_so * 3.0f * (1.0f - th1 * th1);
+                g_q[v * 5 + 2] = g_mu_d;
+                g_q[v * 5 + 3] = g_sd * 3.0f * (1.0f - th3 * th3);
+                g_q[v * 5 + 4] = g_c * 0.1353352832366127f * (1.0f - th4 * th4);
+                if (nll_kl) nll_kl[v] = make_float2(nll, kl);
+                s_nll += nll * m;
+                s_kl += m > 0.0f ? kl : 0.0f;
+                s_m += m;
+            }
+        }
+    }
+    qb::block_partials(red, s_nll, s_kl, s_m, partials);
+}
+
 }  // namespace
 
 extern "C" int qbold_elbo_bwd(const qbold_ctx* ctx, const float* x, const float* mask, const float* q,
@@ -336,6 +640,35 @@ extern "C" int qbold_elbo_bwd(const qbold_ctx* ctx, const float* x, const float*
     const int64_t ntile = (N + vpb - 1) / vpb;
     const int grid = (int)(ntile < qb::elbo_grid(ctx) ? (ntile > 0 ? ntile : 1) : qb::elbo_grid(ctx));
     float2* out = reinterpret_cast<float2*>(nll_kl);
+    // Every T other than 11 / 24 takes elbo_bwd_generic_kernel, which covers what the generic forward does
+    // (qb::elbo_fast_path).  QBOLD_KSEL_ELBO_BWD_GENERIC sends T = 11 / 24 there too where it is an equivalent kernel;
+    // Student-t / log-data contexts keep the specialised kernels under the bit.  At T = 11 / 24 the generic kernel also
+    // takes the specialised kernels' per-wave choice of the KL form (kl_per_wave), so that the two agree voxel by voxel;
+    // at every other T the choice is per voxel and the outputs do not depend on the sharding.
+    const bool spec_T = ctx->dev.T == 11 || ctx->dev.T == 24;
+    if (!spec_T && !qb::elbo_fast_path(ctx)) {
+        qb::set_error("qbold_elbo_bwd: for T other than 11 / 24 only the optimal.yaml configuration (table mode, "
+                      "Gaussian likelihood, linear data) is built");
+        return QBOLD_ERR_UNSUPPORTED;
+    }
+    if (!spec_T || ((ctx->kernel_sel & QBOLD_KSEL_ELBO_BWD_GENERIC) && qb::elbo_fast_path(ctx))) {
+        const int T = ctx->dev.T;
+        QB_REQUIRE(T >= 1 && T <= QB_MAX_T, "qbold_elbo_bwd: need 1 <= T <= 64");
+        const int gvpb = kGenBlock / lpv;
+        const int64_t gtile = (N + gvpb - 1) / gvpb;
+        const int ggrid = (int)(gtile < qb::elbo_grid(ctx) ? (gtile > 0 ? gtile : 1) : qb::elbo_grid(ctx));
+        const size_t smem = sizeof(qb::FwdLds) + sizeof(float) * gen_rows(lpv) * (size_t)T * kGenBlock;
+        auto kern = lpv == 1 ? elbo_bwd_generic_kernel<1> : elbo_bwd_generic_kernel<QB_LANES_PER_VOXEL>;
+        if (smem > 64 * 1024)
+            QB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)smem));
+        hipLaunchKernelGGL(kern, dim3(ggrid), dim3(kGenBlock), smem, s, ctx->dev, ctx->d_tab, x, mask, q, prior, log_sigma,
+                           S, K, spec_T ? 1 : 0, seed, voxel0, g_q, g_log_sigma, out, partials, N);
+        QB_HIP(hipGetLastError());
+        hipLaunchKernelGGL(qb::reduce_partials_kernel, dim3(1), dim3(192), 0, s, partials, ggrid, sums);
+        QB_HIP(hipGetLastError());
+        return QBOLD_OK;
+    }
 #define QB_LAUNCH_BWD(TT, SEC)                                                                                          \
     do {                                                                                                                \
         if (lpv == 1)                                                                                                   \

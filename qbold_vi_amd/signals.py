@@ -18,13 +18,18 @@ _NORM_SNR_11 = np.array([0.985, 1.00, 1.01, 1., 0.97, 0.95, 0.93, 0.90, 0.86, 0.
                         dtype=np.float32)
 
 
-def _norm_snr(T):
+def _norm_snr(T, tau_weighted=True):
     if T == 11:
         return _NORM_SNR_11
     if T == 24:
         return (1.0 - (np.abs(np.arange(-0.028, 0.065, 0.004)) * 3.0)).astype(np.float32)
+    if not tau_weighted:
+        # any other protocol with the per-tau weighting switched off in `config`: every tau at the tau = 0 image's
+        # SNR (this package's addition; the reference ignores the key and has no profile to fall back on)
+        return np.ones(T, dtype=np.float32)
     # the reference raises NameError here (signals.py:117-124 defines norm_snr for 11 / 24 only)
-    raise ValueError(f"the reference defines the noise model for 11 or 24 taus only, got {T}")
+    raise ValueError(f"the reference defines the tau-weighted noise model for 11 or 24 taus only, got {T}: "
+                     "set tau_weighted = False in `config` for a flat SNR profile")
 
 
 class SignalGenerationLayer:
@@ -98,7 +103,7 @@ class SignalGenerationLayer:
         if self._simulate_noise:
             flat = signal.reshape(-1, signal.shape[-1])
             # every call draws fresh noise, as tf.random does (signals.py:124,128)
-            self._ctx.add_noise(flat, _norm_snr(flat.shape[-1]), 50.0, 120.0,
+            self._ctx.add_noise(flat, _norm_snr(flat.shape[-1], self._weighted_noise), 50.0, 120.0,
                                 seed=self._seed + 7919 * self._calls)
             self._calls += 1
         return signal
