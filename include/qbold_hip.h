@@ -407,6 +407,49 @@ int qbold_log_evidence_bwd(const qbold_ctx* ctx, const float* x, const float* ma
                            int64_t voxel0, float* g_q, float* g_log_sigma, float* out, double* sums,
                            void* workspace, int64_t N, void* stream);
 
+/* The per-draw rows behind qbold_log_evidence_fwd, unreduced (this package's addition): the K draws of that entry
+ * (explicit z [N][K][2], or the Philox stream 6 keyed (seed, voxel0 + i): draw k of this call is draw k there) and per
+ * draw
+ *   log_w [N][K] = -nll - (log q - log p), the value qbold_log_evidence_fwd folds into its log-sum-exp
+ *   theta [N][K][3] or NULL: (OEF, DBV, R2') of the draw.
+ * No sums, no workspace.  Voxels with mask <= 0 (or NaN) are not read and their rows are filled with NaN; mask NULL =
+ * ones.  A voxel's rows are the same bits at any batch position and under any sharding by voxel0.
+ * Table mode: T = 11 / 24 with every likelihood switch (Student-t, log data, three-image normalisation), every other
+ * T <= 64 on the configuration of qbold_log_evidence_fwd's generic kernel (Gaussian likelihood, linear data); the
+ * literal tissue mode and anything else: QBOLD_ERR_UNSUPPORTED.  QBOLD_ERR_INVALID for K < 1, K > QBOLD_IW_MAX_K, a
+ * NULL log_w or a NULL input buffer.  x, q, prior, sigma, stream as qbold_log_evidence_fwd. */
+int qbold_log_evidence_draws(const qbold_ctx* ctx, const float* x, const float* mask, const float* q,
+                             const float* prior, const float* sigma, const float* z, int K, uint64_t seed,
+                             int64_t voxel0, float* log_w, float* theta, int64_t N, void* stream);
+
+/* Pareto-smoothed importance sampling (Vehtari, Simpson, Gelman, Yao, Gabry, JMLR 2024) of N independent rows of K
+ * log-weights (this package's addition; nothing of the qBOLD model enters).
+ *   log_w [N][K]: any finite values; -inf is a zero weight; a NaN (or +inf, or no finite value) anywhere in a row makes
+ *     that row's outputs NaN.
+ *   theta [N][K][C] or NULL, 1 <= C <= QBOLD_PSIS_MAX_C: per-draw quantities to average.
+ *   mask [N] or NULL (= ones): rows with mask <= 0 (or NaN) are not read; their outputs are NaN.
+ * Per row, with x = log_w - max:  M = ceil(min(K / 5, 3 sqrt K));  the cutoff c = the (M + 1)-th largest x;  the tail =
+ * the n entries strictly greater than c (ties at the cutoff shorten it), ascending, equal values by ascending draw;
+ * y_r = expm1(x_r - c) (the paper's exp(x) - exp(c) up to the factor exp(c), to which the fit's k is invariant);
+ * Zhang & Stephens' fit: m = 30 + floor(sqrt n) candidates b_j = 1 / y_n + (1 - sqrt(m / (j - 1/2))) / (3 y_q),
+ * q = floor(n / 4 + 1/2), k_j = mean_r log1p(-b_j y_r), L_j = n (log(-b_j / k_j) - k_j - 1), b^ = sum_j softmax(L)_j b_j,
+ * k = mean_r log1p(-b^ y_r), sigma = -k / b^, k^ = (n k + 5) / (n + 10);  the tail entry of rank r becomes
+ * c + log1p(sigma expm1(-k log1p(-p_r)) / k), p_r = (r - 1/2) / n (k = 0: -sigma log1p(-p_r)), truncated at 0, the
+ * largest raw weight; then the row is normalised by its log-sum-exp.  k^ = +inf and the weights stay unsmoothed (but
+ * normalised) when n <= 4, when -c > 80 (beyond float32's exp), or when the fit is not finite.
+ *   out [N][4] = (k^, log p^_PSIS = max + logsumexp(smoothed x) - log K, ESS_PSIS = 1 / sum w~^2, n)
+ *   means [N][C] or NULL (needs theta): sum_k w~_k theta_k
+ *   weights [N][K] or NULL: log w~, normalised.
+ * k^ below min(1 - 1 / log10 K, 0.7) marks a reliable estimate.  Fixed-order sums, no atomics: a row's outputs are the
+ * same bits at any position in the batch.  QBOLD_ERR_INVALID for K outside [QBOLD_PSIS_MIN_K, QBOLD_PSIS_MAX_K] (a
+ * row fits a wave, 16 draws per lane; at 25 the tail has its five points), C outside its range, means without theta,
+ * or a NULL log_w / out. */
+#define QBOLD_PSIS_MIN_K 25
+#define QBOLD_PSIS_MAX_K 1024
+#define QBOLD_PSIS_MAX_C 8
+int qbold_psis(const qbold_ctx* ctx, const float* log_w, const float* theta, int C, const float* mask, int K,
+               float* out, float* means, float* weights, int64_t N, void* stream);
+
 /* Semi-amortised inference (Kim et al. 2018; Cremer et al. 2018): refine each voxel's posterior, starting from given
  * encoder heads, by `steps` gradient steps on that voxel's own objective
  *   E_q[nll(x | y)] + KL(q || prior)   (exact closed-form KL of the logit-space Gaussians, sigma fixed, no TV term)

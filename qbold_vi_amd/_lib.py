@@ -16,6 +16,9 @@ QBOLD_TISSUE_TABLE = 0
 QBOLD_TISSUE_LITERAL = 1
 QBOLD_GRID_OUT = 17   # columns of qbold_posterior_grid's out
 QBOLD_PPC_OUT = 6     # columns of qbold_posterior_predictive's out
+QBOLD_PSIS_MIN_K = 25     # qbold_psis: the draws per row a wave holds
+QBOLD_PSIS_MAX_K = 1024
+QBOLD_PSIS_MAX_C = 8
 
 
 class QboldError(RuntimeError):
@@ -131,6 +134,8 @@ SIGNATURES = {
                                    C.c_double, C.c_double, _I64, _P]),
     "qbold_log_evidence_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
     "qbold_log_evidence_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _P, _I64, _P]),
+    "qbold_log_evidence_draws": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _I64, _P]),
+    "qbold_psis": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _I64, _P]),
     "qbold_posterior_grid": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GridCfg), _P, _P, _P, _P, _I64, _P]),
     "qbold_posterior_predictive": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
     "qbold_refine_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(RefineCfg), _U64,

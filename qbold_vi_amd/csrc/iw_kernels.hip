@@ -475,3 +475,314 @@ extern "C" int qbold_log_evidence_fwd(const qbold_ctx* ctx, const float* x, cons
     QB_HIP(hipGetLastError());
     return QBOLD_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// qbold_log_evidence_draws: the same draws, unreduced.  The kernels above with a storing sink in place of the streaming
+// log-sum-exp: same lane mapping (lane group g owns draws 4 g .. 4 g + 3 of a Philox call), per-draw arithmetic restated
+// from iw_draws / iw_fwd_generic_kernel, each draw's log w and (OEF, DBV, R2') kept until its call is complete and then
+// stored as one 16-byte piece of the log_w row and three of the theta row (element stores when K is no multiple of 4,
+// where rows are not 16-byte aligned, and for a short last call).  Voxels with mask <= 0 (or NaN) are not read; their
+// rows are NaN.  The kernels above are untouched.
+namespace {
+
+struct IwRowSink {
+    float* __restrict__ lw;   // this voxel's log_w row [K]
+    float* __restrict__ th;   // this voxel's theta row [K][3] or nullptr
+    bool vec;                 // rows 16-byte aligned
+    float l[4], t[12];        // the call's draws so far, the newest last
+    __device__ __forceinline__ void push(float lwk, float oef, float dbv, float r2p) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) l[i] = l[i + 1];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) t[i] = t[i + 3];
+        l[3] = lwk;
+        t[9] = oef;
+        t[10] = dbv;
+        t[11] = r2p;
+    }
+    // the call's first draw d0 (a multiple of 4) and how many it had: they sit in the last cnt slots
+    __device__ __forceinline__ void flush(int d0, int cnt) {
+        if (cnt == 4 && vec) {
+            *reinterpret_cast<float4*>(lw + d0) = make_float4(l[0], l[1], l[2], l[3]);
+            if (th) {
+                float4* p = reinterpret_cast<float4*>(th + 3 * d0);
+                p[0] = make_float4(t[0], t[1], t[2], t[3]);
+                p[1] = make_float4(t[4], t[5], t[6], t[7]);
+                p[2] = make_float4(t[8], t[9], t[10], t[11]);
+            }
+            return;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int d = d0 + i - (4 - cnt);
+            if (i >= 4 - cnt) {
+                lw[d] = l[i];
+                if (th) {
+                    th[3 * d + 0] = t[3 * i + 0];
+                    th[3 * d + 1] = t[3 * i + 1];
+                    th[3 * d + 2] = t[3 * i + 2];
+                }
+            }
+        }
+    }
+};
+
+// NaN rows of a voxel outside the mask, its four lanes taking the draws they own
+__device__ __forceinline__ void iw_nan_rows(int K, int part, float* __restrict__ lw, float* __restrict__ th) {
+    const float nan = __uint_as_float(0x7fc00000u);
+    for (int g = part; 4 * g < K; g += QB_LANES_PER_VOXEL)
+        for (int d = 4 * g; d < 4 * g + 4 && d < K; ++d) {
+            lw[d] = nan;
+            if (th) th[3 * d + 0] = th[3 * d + 1] = th[3 * d + 2] = nan;
+        }
+}
+
+// iw_draws with the sink
+template <int T, int SE, bool FAST, bool MIR, bool WHITEN, class LDS>
+__device__ __forceinline__ void iw_draws_to_rows(const LDS* L, const QbDev& c, const qb::VoxelLik<T>& lik,
+                                               const qb::LogitMvn& q, const qb::LogitMvn& p, const IwKl& kl, int K,
+                                               const float* __restrict__ zv, uint64_t seed, uint64_t vox, int part,
+                                               IwRowSink& sink) {
+    const int n = iw_lane_draws(K, part);
+    qb::DrawQuad dq;
+    uint32_t g = (uint32_t)part;
+#pragma unroll 1
+    for (int i = 0; i < n; ++i) {
+        float z0, z1;
+        if (zv) {
+            const int draw = 4 * (part + 4 * (i >> 2)) + (i & 3);
+            z0 = zv[2 * draw];
+            z1 = zv[2 * draw + 1];
+        } else {
+            if ((i & 3) == 0) {
+                dq.load(seed, vox, g, kStreamIw);
+                g += QB_LANES_PER_VOXEL;
+            }
+            dq.next(z0, z1);
+        }
+        float a, b, oef, dbv, nll;
+        qb::reparam_logits(q, z0, z1, a, b);
+        if constexpr (FAST && qb::IsGtLds<LDS>::value) {
+            const float sa = qb::sigmoidf_(a), sb = qb::sigmoidf_(b);
+            nll = fmaf(0.5f, qb::sample_sq_fast<T, SE>(L, c, lik, sa, sb), lik.log_s_sum);
+            oef = fmaf(sa, QB_OEF_RANGE, QB_MIN_OEF);
+            dbv = fmaf(sb, QB_DBV_RANGE, QB_MIN_DBV);
+        } else {
+            qb::forward_transform(a, b, oef, dbv);
+            if constexpr (FAST) nll = fmaf(0.5f, qb::sample_sq_fast<T, SE, MIR>(L, c, lik, oef, dbv), lik.log_s_sum);
+            else nll = qb::sample_nll<T, SE, false>(L, c, lik, oef, dbv);
+        }
+        float dswr = iw_dswr(kl, z0, z1);   // swr_p - swr_q
+        if (!WHITEN && fmaxf(fabsf(a), fabsf(b)) > QB_LOGIT_CLIP) dswr = qb::kl_swr_diff(q, p, z0, z1);
+        sink.push(-nll - fmaf(0.5f, dswr, kl.cst), oef, dbv, (c.dw_coef * oef) * dbv);
+        if ((i & 3) == 3 || i == n - 1) sink.flush(4 * (part + 4 * (i >> 2)), (i & 3) + 1);
+    }
+}
+
+// T = 11 / 24: iw_fwd_kernel's template switches and dispatch (table mode only)
+template <int T, int SE, bool FAST, bool GT = false, bool MIR = false>
+__global__ __launch_bounds__(kBlock) void iw_draws_kernel(
+    QbDev c, const float4* __restrict__ g_tab, const float* __restrict__ x, const float* __restrict__ mask,
+    const float* __restrict__ q, const float* __restrict__ prior, const float* __restrict__ sigma,
+    const float* __restrict__ z, int K, uint64_t seed, int64_t voxel0, float* __restrict__ log_w,
+    float* __restrict__ theta, bool vec, int64_t N) {
+    static_assert(!GT || (FAST && SE >= 0 && qb::gtab_segs(T) > 0), "GT needs the fast path with a compile-time spin echo");
+    static_assert(!MIR || (FAST && SE >= 0), "merged mirror pairs: fast path with a compile-time spin echo");
+    constexpr bool kMir = GT || MIR;
+    using Lds = typename IwLds<T, SE, GT>::type;
+    __shared__ Lds L;
+    if constexpr (qb::IsGtLds<Lds>::value) {
+        qb::gt_lds_fill(&L, g_tab, c);
+    } else {
+        qb::fwd_lds_fill(&L, g_tab, true);
+        if (threadIdx.x < QB_MAX_T) L.blood_B[threadIdx.x] = c.blood_B[threadIdx.x];
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int part = lane >> 4;
+    const int64_t ntile = (N + kVoxPerBlock - 1) / kVoxPerBlock;
+    for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+        const int64_t v = tile * kVoxPerBlock + wave * QB_VOX_PER_WAVE + (lane & 15);
+        if (v >= N) continue;
+        IwRowSink sink = {};
+        sink.lw = log_w + v * K;
+        sink.th = theta ? theta + v * K * 3 : nullptr;
+        sink.vec = vec;
+        const float m = mask ? mask[v] : 1.0f;
+        if (!(m > 0.0f)) {
+            iw_nan_rows(K, part, sink.lw, sink.th);
+            continue;
+        }
+        float xv[T], sv[T], qv[5], pv[5];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            xv[t] = x[v * T + t];
+            sv[t] = sigma[v * T + t];
+        }
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            qv[i] = q[v * 5 + i];
+            pv[i] = prior[v * 5 + i];
+        }
+        qb::VoxelLik<T> lik;
+        qb::prepare_lik<T, SE, false, (FAST && SE >= 0), FAST, kMir>(c, xv, sv, m, lik);
+        const qb::LogitMvn qm = qb::make_mvn(qv), pm = qb::make_mvn(pv);
+        const IwKl kl = make_iw_kl(qm, pm);
+        const float* zv = z ? z + v * (int64_t)K * 2 : nullptr;
+        const uint64_t vox = (uint64_t)(voxel0 + v);
+        // the choice is per wave over its voxels inside the mask; a draw that the whitened form covers has the same
+        // bits in both loops, so a voxel's rows do not depend on its neighbours
+        if (iw_whiten(qm, zv))
+            iw_draws_to_rows<T, SE, FAST, kMir, true>(&L, c, lik, qm, pm, kl, K, zv, seed, vox, part, sink);
+        else
+            iw_draws_to_rows<T, SE, FAST, kMir, false>(&L, c, lik, qm, pm, kl, K, zv, seed, vox, part, sink);
+    }
+}
+
+// Any other tau count: iw_fwd_generic_kernel with the sink
+__global__ __launch_bounds__(kGenBlock) void iw_draws_generic_kernel(
+    QbDev c, const float4* __restrict__ g_tab, const float* __restrict__ x, const float* __restrict__ mask,
+    const float* __restrict__ q, const float* __restrict__ prior, const float* __restrict__ sigma,
+    const float* __restrict__ z, int K, uint64_t seed, int64_t voxel0, float* __restrict__ log_w,
+    float* __restrict__ theta, bool vec, int64_t N) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    qb::FwdLds* L = reinterpret_cast<qb::FwdLds*>(smem);
+    float* yt = reinterpret_cast<float*>(smem + sizeof(qb::FwdLds));   // [T][kGenVox]
+    float* is = yt + QB_MAX_T * kGenVox;                                // [T][kGenVox]
+    qb::fwd_lds_fill(L, g_tab, false);
+    if (threadIdx.x < QB_MAX_T) L->blood_B[threadIdx.x] = c.blood_B[threadIdx.x];
+    __syncthreads();
+
+    const int T = c.T, se = c.se_idx;
+    const bool mirrored = !c.multi_norm && fmaf((float)se, c.tauh_step, c.tauh0) == 0.0f;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int part = lane >> 4;
+    const int vl = wave * QB_VOX_PER_WAVE + (lane & 15);
+    const int64_t ntile = (N + kGenVox - 1) / kGenVox;
+    for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
+        const int64_t v = tile * kGenVox + vl;
+        const bool inb = v < N;
+        const float m = inb ? (mask ? mask[v] : 1.0f) : 0.0f;
+        const bool live = m > 0.0f;
+        const int64_t vc = inb ? v : N - 1;
+        const float* xv = x + vc * T;
+        const float* sv = sigma + vc * T;
+        float ls = 0.0f;
+        __syncthreads();   // previous tile's readers are done
+        if (live) {
+            const float nt = c.multi_norm ? (xv[se - 1] + xv[se] + xv[se + 1]) / 3.0f + 1e-3f : xv[se] + 1e-3f;
+            const float inv_nt = qb::rcpf_(nt);
+            for (int t = part; t < T; t += QB_LANES_PER_VOXEL) {
+                yt[t * kGenVox + vl] = xv[t] * inv_nt;
+                is[t * kGenVox + vl] = qb::rcpf_(sv[t]);
+                ls += QB_LN2 * qb::log2f_(sv[t]);
+            }
+        }
+        const float log_s_sum = qb::voxel_sum(ls) + (float)T * 0.9189385332046727f;
+        __syncthreads();
+        if (inb && !live) iw_nan_rows(K, part, log_w + v * K, theta ? theta + v * K * 3 : nullptr);
+        if (live) {
+            float qv[5], pv[5];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                qv[i] = q[v * 5 + i];
+                pv[i] = prior[v * 5 + i];
+            }
+            const qb::LogitMvn qm = qb::make_mvn(qv), pm = qb::make_mvn(pv);
+            const IwKl kl = make_iw_kl(qm, pm);
+            const float* zv = z ? z + v * (int64_t)K * 2 : nullptr;
+            const bool whiten = iw_whiten(qm, zv);
+            const uint64_t vox = (uint64_t)(voxel0 + v);
+            IwRowSink sink = {};
+            sink.lw = log_w + v * K;
+            sink.th = theta ? theta + v * K * 3 : nullptr;
+            sink.vec = vec;
+            const int n = iw_lane_draws(K, part);
+            qb::DrawQuad dq;
+            uint32_t g = (uint32_t)part;
+            for (int i = 0; i < n; ++i) {
+                float z0, z1;
+                if (zv) {
+                    const int draw = 4 * (part + 4 * (i >> 2)) + (i & 3);
+                    z0 = zv[2 * draw];
+                    z1 = zv[2 * draw + 1];
+                } else {
+                    if ((i & 3) == 0) {
+                        dq.load(seed, vox, g, kStreamIw);
+                        g += QB_LANES_PER_VOXEL;
+                    }
+                    dq.next(z0, z1);
+                }
+                float a, b, oef, dbv;
+                qb::reparam_logits(qm, z0, z1, a, b);
+                qb::forward_transform(a, b, oef, dbv);
+                const qb::FwdFast fv = qb::fwd_fast(c, oef, dbv);
+                const float nll = generic_half_sq(L, c, fv, yt, is, vl, T, se, mirrored) + log_s_sum;
+                float dswr = iw_dswr(kl, z0, z1);
+                if (!whiten && fmaxf(fabsf(a), fabsf(b)) > QB_LOGIT_CLIP) dswr = qb::kl_swr_diff(qm, pm, z0, z1);
+                sink.push(-nll - fmaf(0.5f, dswr, kl.cst), oef, dbv, (c.dw_coef * oef) * dbv);
+                if ((i & 3) == 3 || i == n - 1) sink.flush(4 * (part + 4 * (i >> 2)), (i & 3) + 1);
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int qbold_log_evidence_draws(const qbold_ctx* ctx, const float* x, const float* mask, const float* q,
+                                        const float* prior, const float* sigma, const float* z, int K, uint64_t seed,
+                                        int64_t voxel0, float* log_w, float* theta, int64_t N, void* stream) {
+    QB_NEED_DEVICE(ctx);
+    QB_REQUIRE(N >= 0 && K >= 1 && K <= QBOLD_IW_MAX_K,
+               "qbold_log_evidence_draws: need N >= 0 and 1 <= K <= QBOLD_IW_MAX_K");
+    QB_REQUIRE(log_w, "qbold_log_evidence_draws: null log_w");
+    QB_REQUIRE(N == 0 || (x && q && prior && sigma), "qbold_log_evidence_draws: null input buffer");
+    hipStream_t s = (hipStream_t)stream;
+    const bool fast = qb::elbo_fast_path(ctx);
+    if (ctx->dev.tissue_mode == QBOLD_TISSUE_LITERAL || (!fast && ctx->dev.T != 11 && ctx->dev.T != 24)) {
+        qb::set_error("qbold_log_evidence_draws: built for table mode; for T other than 11 / 24 only the optimal.yaml "
+                      "configuration (Gaussian likelihood, linear data)");
+        return QBOLD_ERR_UNSUPPORTED;
+    }
+    if (N == 0) return QBOLD_OK;
+    const bool vec = (K & 3) == 0 && (reinterpret_cast<uintptr_t>(log_w) & 15) == 0 &&
+                     (reinterpret_cast<uintptr_t>(theta) & 15) == 0;
+    const int64_t ntile = (N + kVoxPerBlock - 1) / kVoxPerBlock;
+    int grid = (int)(ntile < qb::elbo_grid(ctx) ? ntile : qb::elbo_grid(ctx));
+    const bool gt = ctx->gtab_ok && !(ctx->kernel_sel & 8) && qb::gtab_segs(ctx->dev.T) > 0;
+#define QB_LAUNCH_DRAWS(TT, SE, FAST, GT, MIR, TAB)                                                                   \
+    hipLaunchKernelGGL((iw_draws_kernel<TT, SE, FAST, GT, MIR>), dim3(grid), dim3(kBlock), 0, s, ctx->dev, TAB, x,    \
+                       mask, q, prior, sigma, z, K, seed, voxel0, log_w, theta, vec, N)
+    // the dispatch of qbold_log_evidence_fwd, table mode
+    switch (ctx->dev.T) {
+        case 11:
+            if (fast && ctx->dev.se_idx == 2 && !ctx->dev.multi_norm && gt)
+                QB_LAUNCH_DRAWS(11, 2, true, (qb::gtab_segs(11) > 0), false, ctx->d_gtab);
+            else if (fast && ctx->dev.se_idx == 2 && !ctx->dev.multi_norm && ctx->grid_mirrors)
+                QB_LAUNCH_DRAWS(11, 2, true, false, true, ctx->d_tab);
+            else if (fast && ctx->dev.se_idx == 2 && !ctx->dev.multi_norm) QB_LAUNCH_DRAWS(11, 2, true, false, false, ctx->d_tab);
+            else if (fast) QB_LAUNCH_DRAWS(11, -1, true, false, false, ctx->d_tab);
+            else QB_LAUNCH_DRAWS(11, -1, false, false, false, ctx->d_tab);
+            break;
+        case 24:
+            if (fast && ctx->dev.se_idx == 7 && !ctx->dev.multi_norm && gt)
+                QB_LAUNCH_DRAWS(24, 7, true, (qb::gtab_segs(24) > 0), false, ctx->d_gtab);
+            else if (fast && ctx->dev.se_idx == 7 && !ctx->dev.multi_norm && ctx->grid_mirrors)
+                QB_LAUNCH_DRAWS(24, 7, true, false, true, ctx->d_tab);
+            else if (fast && ctx->dev.se_idx == 7 && !ctx->dev.multi_norm) QB_LAUNCH_DRAWS(24, 7, true, false, false, ctx->d_tab);
+            else if (fast) QB_LAUNCH_DRAWS(24, -1, true, false, false, ctx->d_tab);
+            else QB_LAUNCH_DRAWS(24, -1, false, false, false, ctx->d_tab);
+            break;
+        default: {
+            const int64_t gtile = (N + kGenVox - 1) / kGenVox;
+            grid = (int)(gtile < qb::elbo_grid(ctx) ? gtile : qb::elbo_grid(ctx));
+            const size_t smem = sizeof(qb::FwdLds) + sizeof(float) * 2 * QB_MAX_T * kGenVox;
+            hipLaunchKernelGGL(iw_draws_generic_kernel, dim3(grid), dim3(kGenBlock), smem, s, ctx->dev, ctx->d_tab, x,
+                               mask, q, prior, sigma, z, K, seed, voxel0, log_w, theta, vec, N);
+        }
+    }
+#undef QB_LAUNCH_DRAWS
+    QB_HIP(hipGetLastError());
+    return QBOLD_OK;
+}

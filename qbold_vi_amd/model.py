@@ -249,7 +249,8 @@ class FineTuner:
         return dict(sums=sums, q=q, nll_kl=nll_kl, nll=sums[0] / sums[2], kl=sums[1] / sums[2],
                     elbo=(sums[0] + sums[1]) / sums[2])
 
-    def log_evidence(self, data, mask, prior, no_samples=100, seed=1, voxel0=0, want_means=False, q=None):
+    def log_evidence(self, data, mask, prior, no_samples=100, seed=1, voxel0=0, want_means=False, q=None, psis=False,
+                     psis_chunk=None):
         """Importance-weighted evidence (Burda et al. 2016) of `no_samples` = K draws per voxel from the fitted
         posterior, on the encoder heads of encoder_model.predict (as the spatial branch of elbo() takes them) and the
         homoscedastic sigma when the fine tuner carries one.  Per voxel, shaped like the data's spatial dims:
@@ -259,8 +260,19 @@ class FineTuner:
           is_means      [..., 3] self-normalised posterior means of (OEF, DBV, R2') (want_means) or None
         and the masked sums (distributed.allreduce_sums reduces them across shards) with mean_log_evidence,
         mean_elbo and gap = mean_log_evidence - mean_elbo (an estimate of the mean KL(q || p(z | x))).
-        q: heads [..., 5] to evaluate instead of the encoder's (refine()'s output, say); sigma as above."""
+        q: heads [..., 5] to evaluate instead of the encoder's (refine()'s output, say); sigma as above.
+        psis=True (needs 25 <= no_samples <= 1024): Pareto-smoothed importance sampling (Vehtari et al. 2024) of the
+        SAME draws (Context.log_evidence_draws + Context.psis), which adds
+          khat               the tail shape k^ of the voxel's weights: the estimates above are reliable below
+                             khat_threshold = min(1 - 1 / log10 K, 0.7); above 0.7 no K will save them
+          log_evidence_psis  log p^ from the smoothed weights
+          ess_psis           1 / sum w~^2 of the smoothed normalised weights
+          psis_means         [..., 3] the smoothed-weight means of (OEF, DBV, R2')
+        (NaN outside the mask), computed in voxel chunks whose per-draw buffers stay under 256 MiB (psis_chunk: voxels
+        per chunk instead); chunks pass their own voxel0, so the result does not depend on the chunking."""
         from .distributed import log_evidence_from_sums
+        if psis and not 25 <= int(no_samples) <= 1024:   # QBOLD_PSIS_MIN_K, QBOLD_PSIS_MAX_K
+            raise ValueError("log_evidence(psis=True) needs 25 <= no_samples <= 1024")
         tr = self._trainer
         self._check_mvn_family("log_evidence")
         T = data.shape[-1]
@@ -272,9 +284,27 @@ class FineTuner:
                                                 want_means=want_means)
         lead = data.shape[:-1]
         lp, el, gap = log_evidence_from_sums(sums)
-        return dict(log_evidence=out[:, 0].reshape(lead), elbo=out[:, 1].reshape(lead), ess=out[:, 2].reshape(lead),
-                    is_means=None if means is None else means.reshape(lead + (3,)), sums=sums,
-                    mean_log_evidence=lp, mean_elbo=el, gap=gap)
+        res = dict(log_evidence=out[:, 0].reshape(lead), elbo=out[:, 1].reshape(lead), ess=out[:, 2].reshape(lead),
+                   is_means=None if means is None else means.reshape(lead + (3,)), sums=sums,
+                   mean_log_evidence=lp, mean_elbo=el, gap=gap)
+        if psis:
+            from .ops import psis_khat_threshold
+            K, N = int(no_samples), x.shape[0]
+            chunk = int(psis_chunk) if psis_chunk else max((256 << 20) // (16 * K) - 1, 1)   # log_w + theta: 16 K bytes
+            if chunk < 1:
+                raise ValueError("psis_chunk must be positive")
+            po = torch.empty((N, 4), dtype=torch.float32, device=x.device)
+            pm = torch.empty((N, 3), dtype=torch.float32, device=x.device)
+            for a in range(0, N, chunk):
+                b = min(a + chunk, N)
+                mc = None if m is None else m[a:b]
+                lw, th = tr._ctx.log_evidence_draws(x[a:b], mc, q[a:b], p5[a:b], sg[a:b], K, seed=seed,
+                                                    voxel0=voxel0 + a, want_theta=True)
+                po[a:b], pm[a:b], _ = tr._ctx.psis(lw, th, mc)
+            res.update(khat=po[:, 0].reshape(lead), log_evidence_psis=po[:, 1].reshape(lead),
+                       ess_psis=po[:, 2].reshape(lead), psis_means=pm.reshape(lead + (3,)),
+                       khat_threshold=psis_khat_threshold(K))
+        return res
 
     def _check_mvn_family(self, what):
         if not self._trainer._use_mvg:
@@ -738,7 +768,7 @@ class EncoderTrainer:
 
     def save_predictions(self, model, data, filename, transform_directory=None, use_first_op=True,
                          fine_tuner_model=None, priors=None, iw_samples=None, refine_steps=None,
-                         posterior_grid=None, ppc_samples=None, refine_smoothness_weight=0.0):
+                         posterior_grid=None, ppc_samples=None, refine_smoothness_weight=0.0, psis=False):
         """model.py:772-887: write `<filename>_{oef,dbv,r2p,logstds}.nii.gz` (posterior means of
         OEF / DBV / R2' over 200 draws and their variances) and, with a fine tuner,
         `_likelihood` (per-voxel NLL averaged over 100 stochastic passes), `_kl` (100-draw KL to
@@ -746,6 +776,10 @@ class EncoderTrainer:
         iw_samples = K (with a fine tuner; this package's addition): also `_logevidence` (importance-weighted
         log p^ of K draws, FineTuner.log_evidence), `_vigap` (log p^ - the same draws' ELBO) and `_ess` (effective
         sample size), zero outside the mask; the three maps [subj, X, Y, Z, 1] are returned as a dict.
+        psis = True (with iw_samples = K, 25 <= K <= 1024): Pareto-smoothed importance sampling of the same draws
+        (FineTuner.log_evidence(psis=True)) as `_khat` (the tail shape k^ of the voxel's weights: the importance
+        estimates are reliable below min(1 - 1 / log10 K, 0.7)), `_logevidence_psis`, `_ess_psis` and the smoothed-weight
+        means `_oef_psis`, `_dbv_psis`, `_r2p_psis`, zero outside the mask; these maps join the returned dict.
         refine_steps (with a fine tuner; this package's addition): refine each voxel's heads by that many steps
         (FineTuner.refine) and also write `_oef_refined`, `_dbv_refined`, `_r2p_refined` (calculate_means of the
         refined heads) and `_amortgap` (per-voxel ELBO of the refined heads minus that of the encoder's, both from
@@ -810,15 +844,22 @@ class EncoderTrainer:
             save_im_data((y_true - y_pred).abs().mean(-1, keepdim=True), filename + '_residual')
 
         iw_maps = None
+        if psis and not (fine_tuner_model and iw_samples):
+            raise ValueError("save_predictions(psis=True) smooths the draws of iw_samples: give a fine tuner and iw_samples")
         if fine_tuner_model and iw_samples:
             iw = fine_tuner_model.log_evidence(data[..., :-1], mask,
                                                torch.as_tensor(priors, device=data.device)[..., :self._nq],
-                                               no_samples=int(iw_samples), seed=self._seed + 31)
+                                               no_samples=int(iw_samples), seed=self._seed + 31, psis=bool(psis))
             live = mask[..., 0] > 0
             zero = torch.zeros_like(iw["log_evidence"])
             iw_maps = {k: torch.where(live, v, zero)[..., None] for k, v in
                        (("logevidence", iw["log_evidence"]), ("vigap", iw["log_evidence"] - iw["elbo"]),
                         ("ess", iw["ess"]))}
+            if psis:
+                iw_maps.update({k: torch.where(live, v, zero)[..., None] for k, v in
+                                (("khat", iw["khat"]), ("logevidence_psis", iw["log_evidence_psis"]),
+                                 ("ess_psis", iw["ess_psis"]), ("oef_psis", iw["psis_means"][..., 0]),
+                                 ("dbv_psis", iw["psis_means"][..., 1]), ("r2p_psis", iw["psis_means"][..., 2]))})
             for k, v in iw_maps.items():
                 save_im_data(v, filename + '_' + k)
 

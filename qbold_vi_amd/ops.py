@@ -67,6 +67,14 @@ def merge_ranges(pieces):
     return [tuple(r) for r in out]
 
 
+def psis_khat_threshold(K):
+    """min(1 - 1 / log10 K, 0.7): the k^ below which K draws give a reliable PSIS estimate (Vehtari et al. 2024)."""
+    K = int(K)
+    if K < 2:
+        raise ValueError("psis_khat_threshold: need K >= 2")
+    return min(1.0 - 1.0 / math.log10(K), 0.7)
+
+
 class EncoderWeights:
     """The canonical (Keras-orientation) weight blob of the voxel-wise encoder plus its
     MFMA-ordered device copy.  Layout: include/qbold_hip.h, qbold_encoder_num_params."""
@@ -506,6 +514,54 @@ class Context:
                                                    _ptr(out), _ptr(sums), _ptr(self._workspace()), N, _stream()),
                    "qbold_log_evidence_bwd")
         return sums, gq, gls, out
+
+    def log_evidence_draws(self, x, mask, q, prior, sigma, K, z=None, seed=1, voxel0=0, want_theta=False):
+        """The per-draw rows behind log_evidence (qbold_log_evidence_draws; the same K draws for the same seed and
+        voxel0, Philox stream 6 unless z [N, K, 2] is given), unreduced.  Returns (log_w [N, K] = -nll - (log q - log p)
+        of each draw, theta [N, K, 3] = the draw's (OEF, DBV, R2') or None).  Voxels with mask <= 0 are not read; their
+        rows are NaN."""
+        x = _f32(x, "x", self.T)
+        N = x.numel() // self.T
+        q = _f32(q, "q", 5)
+        prior = _f32(prior, "prior", 5)
+        sigma = _f32(sigma, "sigma", self.T)
+        mask = _f32(mask, "mask") if mask is not None else None
+        z = _f32(z, "z", 2) if z is not None else None
+        if z is not None and z.numel() != N * K * 2:
+            raise ValueError("z must be [N, K, 2]")
+        K = int(K)
+        log_w = torch.empty((N, max(K, 0)), dtype=torch.float32, device=x.device)
+        theta = torch.empty((N, max(K, 0), 3), dtype=torch.float32, device=x.device) if want_theta else None
+        _lib.check(self.lib.qbold_log_evidence_draws(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior),
+                                                     _ptr(sigma), _ptr(z), K, int(seed), int(voxel0), _ptr(log_w),
+                                                     _ptr(theta), N, _stream()), "qbold_log_evidence_draws")
+        return log_w, theta
+
+    def psis(self, log_w, theta=None, mask=None, want_weights=False):
+        """Pareto-smoothed importance sampling of the rows of log_w [N, K], 25 <= K <= 1024 (qbold_psis; Vehtari et
+        al. 2024).  theta [N, K, C] (C <= 8): per-draw quantities to average; rows with mask <= 0 are not read.
+        Returns (out [N, 4] = (k^, log p^_PSIS, ESS_PSIS, tail length n), means [N, C] = sum_k w~_k theta_k or None,
+        weights [N, K] = the normalised smoothed log-weights (want_weights) or None).  k^ below
+        psis_khat_threshold(K) marks a reliable estimate; above 0.7 no K will save it."""
+        log_w = _f32(log_w, "log_w")
+        if log_w.dim() != 2:
+            raise ValueError("log_w must be [N, K]")
+        N, K = log_w.shape
+        C = 0
+        if theta is not None:
+            theta = _f32(theta, "theta")
+            if theta.dim() != 3 or theta.shape[:2] != log_w.shape:
+                raise ValueError("theta must be [N, K, C]")
+            C = theta.shape[2]
+        mask = _f32(mask, "mask") if mask is not None else None
+        if mask is not None and mask.numel() != N:
+            raise ValueError("mask must hold N values")
+        out = torch.empty((N, 4), dtype=torch.float32, device=log_w.device)
+        means = torch.empty((N, C), dtype=torch.float32, device=log_w.device) if theta is not None else None
+        weights = torch.empty((N, K), dtype=torch.float32, device=log_w.device) if want_weights else None
+        _lib.check(self.lib.qbold_psis(self.handle, _ptr(log_w), _ptr(theta), int(C), _ptr(mask), int(K), _ptr(out),
+                                       _ptr(means), _ptr(weights), N, _stream()), "qbold_psis")
+        return out, means, weights
 
     def refine_posterior(self, x, mask, q, prior, sigma, steps=200, S=1, lr=0.1, lr_final=None, optimizer="adam",
                          betas=(0.9, 0.999), eps=1e-8, z=None, seed=1, voxel0=0, want_loss=False):

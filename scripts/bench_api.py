@@ -95,6 +95,32 @@ def main():
 
     def sbytes(TT):   # per step: x, sigma, heads, moments, loss, prior, mask, neighbours' heads 0, 2 and masks in; 68 out
         return 4 * (2 * TT + 21) + 68
+    # PSIS diagnostics on 262,144 voxels (at 1 M voxels the per-draw rows of K = 256 take 4 GiB): the row dump, the
+    # Pareto fit on ready rows, both, and log_evidence on the same voxels and draws beside them
+    nq = 1 << 18
+    xq, mq, qq_, pq, sq = x[:nq], mask[:nq], q[:nq], o1[:nq], sg[:nq]
+    rows = {}
+
+    def ready(K):   # the rows of K draws, dumped once
+        if K not in rows:
+            rows[K] = ctx.log_evidence_draws(xq, mq, qq_, pq, sq, K, seed=1, want_theta=True)
+        return rows[K]
+
+    def draws_psis(K):
+        lw, th = ctx.log_evidence_draws(xq, mq, qq_, pq, sq, K, seed=1, want_theta=True)
+        return ctx.psis(lw, th, mq)
+
+    def psis_rows(K):
+        f = nq / n    # the table's GB/s are per n voxels
+        return {
+            f"log_evidence(K={K},262144)": (lambda: ctx.log_evidence(xq, mq, qq_, pq, sq, K, seed=1, want_means=True),
+                                            (8 * T + 64) * f),
+            f"log_evidence_draws(K={K},262144)": (lambda: ctx.log_evidence_draws(xq, mq, qq_, pq, sq, K, seed=1,
+                                                                                 want_theta=True),
+                                                  (8 * T + 44 + 16 * K) * f),
+            f"psis(K={K},262144)": (lambda: ctx.psis(*ready(K), mq), (16 * K + 32) * f),
+            f"log_evidence_draws+psis(K={K},262144)": (lambda: draws_psis(K), (8 * T + 76 + 32 * K) * f),
+        }
     calls = {
         # name: (callable, algorithmic bytes per voxel)
         "signal_fwd": (lambda: ctx.signal_fwd(y), 8 + 4 * T),
@@ -168,6 +194,8 @@ def main():
         "encoder_spatial_fwd(3x3x1)": (lambda: st.forward_spatial(x5), None),
         "adamw_step(146k params)": (lambda: st.adamw(1e-3, 1e-4), None),
     }
+    calls.update(psis_rows(64))
+    calls.update(psis_rows(256))
     only = [a for a in sys.argv[1:] if not a.startswith("-")]   # name substrings: time only the matching calls
     out = {}
     for name, (fn, bpv) in calls.items():
