@@ -89,6 +89,34 @@ __global__ __launch_bounds__(kBlock) void elbo_fwd_kernel(
 constexpr int kGenBlock = 128;
 constexpr int kGenVox = kGenBlock / QB_LANES_PER_VOXEL;
 
+// The generic kernel's masked sums are double accumulations reduced in a fixed order (iw_kernels.hip's
+// block_partials_d).  Float32 lane partials and a float32 wave sum keep DESIGN section 2's 1e-8 against the per-voxel
+// rows only where thousands of waves average their roundings out; on a few hundred voxels, or with a weighting mask,
+// they are 2e-8 .. 2e-6 away (MEASUREMENTS.md section 19).
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ void block_partials_d(double* red, double a, double b, double m,
+                                                 double* __restrict__ partials) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    a = wave_sum_d(a);
+    b = wave_sum_d(b);
+    m = wave_sum_d(m);
+    if (lane == 0) {
+        red[3 * wave + 0] = a;
+        red[3 * wave + 1] = b;
+        red[3 * wave + 2] = m;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double acc = 0.0;
+        for (int w = 0; w < nw; ++w) acc += red[3 * w + threadIdx.x];
+        partials[3 * blockIdx.x + threadIdx.x] = acc;
+    }
+}
+
 __global__ __launch_bounds__(kGenBlock) void elbo_fwd_generic_kernel(
     QbDev c, const float4* __restrict__ g_tab, const float* __restrict__ x,
     const float* __restrict__ mask, const float* __restrict__ q, const float* __restrict__ prior,
@@ -112,7 +140,7 @@ __global__ __launch_bounds__(kGenBlock) void elbo_fwd_generic_kernel(
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int part = lane >> 4;
     const int vl = wave * QB_VOX_PER_WAVE + (lane & 15);  // voxel slot inside the block
-    float s_nll = 0.0f, s_kl = 0.0f, s_m = 0.0f;
+    double s_nll = 0.0, s_kl = 0.0, s_m = 0.0;
     const int64_t ntile = (N + kGenVox - 1) / kGenVox;
     for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
         const int64_t v = tile * kGenVox + vl;
@@ -210,13 +238,13 @@ __global__ __launch_bounds__(kGenBlock) void elbo_fwd_generic_kernel(
             const float kl = K > 0 ? qb::voxel_sum(kl_sum) / (float)K : 0.0f;
             if (part == 0) {
                 if (nll_kl) nll_kl[v] = make_float2(nll, kl);
-                s_nll += nll * m;
-                s_kl += m > 0.0f ? kl : 0.0f;
-                s_m += m;
+                s_nll += (double)nll * (double)m;       // model.py:564
+                s_kl += m > 0.0f ? (double)kl : 0.0;   // model.py:661
+                s_m += (double)m;
             }
         }
     }
-    qb::block_partials(red, s_nll, s_kl, s_m, partials);
+    block_partials_d(red, s_nll, s_kl, s_m, partials);
 }
 
 // Long protocols with a compile-time tau count and spin-echo index (BASELINE config 3: T = 64, tau = 0 at
