@@ -170,7 +170,9 @@ int qbold_ctx_set_grad_node0(qbold_ctx* ctx, int on);
 #define QBOLD_KSEL_SLAB_SUMS_SEPARATE 2097152 /* crop backward: every weight-gradient slab sum as its own launch instead of the queued ones */
 #define QBOLD_KSEL_DW_BF16_PIECES 4194304     /* layer-wise weight gradients on three bfloat16 pieces per operand instead of two f16 halves */
 #define QBOLD_KSEL_ELBO_BWD_GENERIC 8388608   /* qbold_elbo_bwd at T = 11 / 24: the run-time-T kernel of every other protocol (Gaussian likelihood on linear data; Student-t / log-data contexts keep the specialised kernels) */
-#define QBOLD_KSEL_ALL (4 | 8 | 256 | 512 | 2048 | 4096 | 8192 | 16384 | 32768 | 65536 | 131072 | 262144 | 524288 | 1048576 | 2097152 | 4194304 | 8388608)
+#define QBOLD_KSEL_VI_FOUR_LANE 16777216      /* qbold_vi_fwd: every voxel on the kernel with four lanes per voxel (16-voxel wave tiles) instead of whole balanced rounds of 64-voxel tiles on the one-lane-per-voxel kernel */
+#define QBOLD_KSEL_VI_WHOLE_TILES 33554432   /* qbold_vi_fwd: every whole 64-voxel tile on the one-lane-per-voxel kernel whatever N is (default: whole rounds of num_cus x waves tiles only), the remainder on the four-lane kernel: per-voxel outputs are the same bits either way */
+#define QBOLD_KSEL_ALL (4 | 8 | 256 | 512 | 2048 | 4096 | 8192 | 16384 | 32768 | 65536 | 131072 | 262144 | 524288 | 1048576 | 2097152 | 4194304 | 8388608 | 16777216 | 33554432)
 int qbold_ctx_set_kernel_selection(qbold_ctx* ctx, int mask);
 /* Host-side evaluation of the uploaded table (for tests): F(x) and dF/dx, HOST arrays. */
 int qbold_ctx_table_eval(const qbold_ctx* ctx, const float* host_x, float* host_F, float* host_dF,

@@ -5,6 +5,8 @@
 // Monte-Carlo draws by Philox call (call g -> draws 4g .. 4g+3, qbold_dev.h; call g belongs to lane group
 // g & 3).  Everything a lane needs per voxel lives in registers: T normalised data points, T
 // inverse sigmas, the transformed posterior / prior parameters.
+// The fused kernel's second layout (vi_fwd_kernel_vox: 64 voxels per wave, one lane per voxel) walks the same four
+// shares of a voxel's draws on one lane, in the same order: the LPV template parameter of voxel_mc_sums / kl_draws_fast.
 #pragma once
 // Wave priorities of the sampling phases (s_setprio; the fused kernel runs its encoder phase at 2-3, see
 // vi_kernels.hip).  Measured on the fused kernel at sustained clocks, 1 M voxels: all phases equal 0.597 ms;
@@ -400,13 +402,27 @@ __device__ __forceinline__ float kl_swr_diff(const LogitMvn& q, const LogitMvn& 
 // when
 // |mu| + 4.8549 (|c| + e^s) stays below the clip for both logits (rounds 1-3: 6.7636 with 32-bit uniforms).  Decided per
 // wave (any lane over the bound, or explicit normals: the general loop for all).
+// LPV = lanes per voxel.  4: the wave's 64 lanes hold 16 voxels, and the choice is the wave's.  1: a lane holds a whole
+// voxel and passes its four shares as `part` one after the other; the choice is made per 16-lane row (row_all), so
+// that the voxels of row r, which a four-lane wave would hold together as one tile, take the loop they take there.
+__device__ __forceinline__ bool row_all(bool pred) {   // pred on every active lane of this lane's 16-lane row
+    const unsigned long long fail = __ballot(!pred);
+    int lane = __lane_id();
+    asm volatile("" : "+v"(lane));   // formed where it is used: hoisted, the row would be one more register across the caller's loops
+    return ((fail >> (lane & 48)) & 0xffffull) == 0;
+}
+template <int LPV = QB_LANES_PER_VOXEL>
 __device__ __forceinline__ float kl_draws_fast(const LogitMvn& q, const LogitMvn& prior, int K,
                                                const float* __restrict__ zk, uint64_t seed, uint64_t vox, int part,
                                                int& n_kl) {
+    static_assert(LPV == 1 || LPV == QB_LANES_PER_VOXEL, "four lanes per voxel, or one");
     constexpr float kZMax = QB_Z_MAX;
     const float reach = fmaxf(fabsf(q.mu_o) + kZMax * q.e_so, fabsf(q.mu_d) + kZMax * (fabsf(q.c) + q.e_sd));
     float kl_sum = 0.0f;
-    if (zk == nullptr && __all(reach < QB_LOGIT_CLIP)) {
+    bool whitened;
+    if constexpr (LPV == 1) whitened = zk == nullptr && row_all(reach < QB_LOGIT_CLIP);
+    else whitened = zk == nullptr && __all(reach < QB_LOGIT_CLIP);
+    if (whitened) {
         const float dmu_o = q.mu_o - prior.mu_o, dmu_d = q.mu_d - prior.mu_d;
         const float d0 = dmu_o * prior.i_so, m00 = q.e_so * prior.i_so;
         const float d1 = fmaf(dmu_d, prior.i_sd, dmu_o * prior.i_bl);
@@ -461,13 +477,72 @@ __device__ __forceinline__ float kl_draws_fast(const LogitMvn& q, const LogitMvn
     return kl_sum;
 }
 
+// The likelihood draws of share `part` of one voxel: Philox calls part, part + 4, ... -> draws 4 g .. 4 g + 3 each, the
+// last call possibly short.  Returns their sum of per-draw terms (FAST: sum_t r^2, else the per-draw NLL); n_lik =
+// draws taken.  zs: explicit normals of this voxel ([S][2]) or nullptr for the Philox stream.
+// ONE loop over the draws (a call's words are refilled every fourth trip): nested as calls x draws the register
+// allocator split far more live ranges around the inner loop (612 against 88 bytes of scratch at T = 24).
+// Used by the one-lane-per-voxel path.  The four-lane path of voxel_mc_sums keeps its own copy of this loop in place:
+// called through this function every four-lane kernel comes out with the same instructions on other registers, and
+// those kernels are to stay what they were, listing included.
+template <int T, int SE, bool FAST, bool LITERAL, bool MIR, class LDS>
+__device__ __forceinline__ float lik_draws(const LDS* L, const QbDev& c, const VoxelLik<T>& lik, const LogitMvn& q,
+                                           int S, const float* __restrict__ zs, uint64_t seed, uint64_t vox, int part,
+                                           int& n_lik) {
+    float nll_sum = 0.0f;
+    const int calls = S > 4 * part ? (S - 4 * part + 15) / 16 : 0;           // calls g = part + 4 k < ceil(S / 4)
+    const int last = calls > 0 ? S - 4 * (part + 4 * (calls - 1)) : 0;      // draws of the last call: 1 .. 4
+    n_lik = calls > 0 ? 4 * (calls - 1) + (last < 4 ? last : 4) : 0;
+    DrawQuad dq;
+    uint32_t g = (uint32_t)part;
+#pragma unroll 1
+    for (int i = 0; i < n_lik; ++i) {
+        float z0, z1;
+        if (zs) {
+            const int draw = 4 * (part + 4 * (i >> 2)) + (i & 3);
+            z0 = zs[2 * draw];
+            z1 = zs[2 * draw + 1];
+        } else {
+            if ((i & 3) == 0) {
+                dq.load(seed, vox, g, STREAM_LIK);
+                g += QB_LANES_PER_VOXEL;
+            }
+            dq.next(z0, z1);
+        }
+        float a, b, oef = 0.0f, dbv = 0.0f;
+        reparam_logits(q, z0, z1, a, b);
+        if constexpr (!(FAST && IsGtLds<LDS>::value)) forward_transform(a, b, oef, dbv);
+        if constexpr (FAST && IsGtLds<LDS>::value) {
+            static_assert(!IsGtLds<LDS>::value || MIR, "the per-tau table scores merged mirror pairs");
+            nll_sum += sample_sq_fast<T, SE>(L, c, lik, sigmoidf_(a), sigmoidf_(b));
+        } else if constexpr (FAST) {
+            nll_sum += sample_sq_fast<T, SE, MIR>(L, c, lik, oef, dbv);
+        } else {
+            nll_sum += sample_nll<T, SE, LITERAL>(L, c, lik, oef, dbv);
+        }
+    }
+    return nll_sum;
+}
+
+// The four shares of a voxel added as voxel_sum adds them across the lane groups, (p0 + p1) + (p2 + p3), by the one lane
+// that walks them in order: after share p, `pair` holds p's pair so far and `first` the finished first pair.
+__device__ __forceinline__ void share_sum(int p, float v, float& first, float& pair) {
+    pair = (p & 1) ? pair + v : v;
+    first = p == 1 ? pair : first;
+}
+
 // The two Monte-Carlo sums of one voxel restricted to this lane's share of the draws.
 //   nll_sum = sum over this half's likelihood draws of the per-draw NLL
 //   kl_sum  = sum over this half's KL draws of log q(y) - log p(y)          model.py:596-603
 // zs / zk: explicit normals of this voxel ([S][2] / [K][2]) or nullptr for the Philox stream.
 // FAST: requires c.full_model, table mode, !predict_log, !use_student_t (checked on the host).
 // MIR: `lik` was prepared with merged mirror pairs (prepare_lik<.., MIR>; always with the per-tau table).
-template <int T, int SE, bool FAST, bool LITERAL, bool MIR = false, class LDS>
+// LPV = lanes per voxel, 4 unless the kernel says otherwise.  1 (fast path only): the lane owns the whole voxel, `part`
+// is ignored and nll_sum / kl_sum are the voxel's.  The lane walks the four shares p = 0 .. 3 itself -- each share's
+// draws into a fresh accumulator, in the order and with the arithmetic of the lane of group p, each share closed by
+// the same fmaf, the KL's moment assembly replayed per share -- and adds them in voxel_sum's order: the same bits as
+// voxel_sum over four lanes.  The draws are addressed by (voxel, call, stream), so the stream does not move.
+template <int T, int SE, bool FAST, bool LITERAL, bool MIR = false, int LPV = QB_LANES_PER_VOXEL, class LDS>
 __device__ __forceinline__ void voxel_mc_sums(const LDS* L, const QbDev& c,
                                               const VoxelLik<T>& lik, const LogitMvn& q,
                                               const float* __restrict__ prior_row, int S, int K,
@@ -475,6 +550,7 @@ __device__ __forceinline__ void voxel_mc_sums(const LDS* L, const QbDev& c,
                                               const float* __restrict__ zk, uint64_t seed,
                                               uint64_t vox, int part, float& nll_sum,
                                               float& kl_sum) {
+    static_assert(LPV == QB_LANES_PER_VOXEL || (LPV == 1 && FAST), "one lane per voxel: built for the fast path");
     nll_sum = 0.0f;
     kl_sum = 0.0f;
     int n_lik = 0, n_kl = 0;  // draws taken by this lane
@@ -483,10 +559,15 @@ __device__ __forceinline__ void voxel_mc_sums(const LDS* L, const QbDev& c,
     // through the loop that owns the register budget).
     const float q_s_sum = q.s_o + q.s_d;
     __builtin_amdgcn_s_setprio(QB_PRIO_LIK);
-    // This lane's draws: Philox calls part, part + 4, ... -> draws 4 g .. 4 g + 3 each, the last call possibly short.
-    // ONE loop over them (a call's words are refilled every fourth trip): nested as calls x draws the register
-    // allocator split far more live ranges around the inner loop (612 against 88 bytes of scratch at T = 24).
-    {
+    if constexpr (LPV == 1) {
+        float first = 0.0f, pair = 0.0f;
+#pragma unroll 1
+        for (int p = 0; p < QB_LANES_PER_VOXEL; ++p) {
+            const float sq = lik_draws<T, SE, FAST, LITERAL, MIR>(L, c, lik, q, S, zs, seed, vox, p, n_lik);
+            share_sum(p, fmaf(0.5f, sq, (float)n_lik * lik.log_s_sum), first, pair);
+        }
+        nll_sum = first + pair;
+    } else {
         const int calls = S > 4 * part ? (S - 4 * part + 15) / 16 : 0;           // calls g = part + 4 k < ceil(S / 4)
         const int last = calls > 0 ? S - 4 * (part + 4 * (calls - 1)) : 0;      // draws of the last call: 1 .. 4
         n_lik = calls > 0 ? 4 * (calls - 1) + (last < 4 ? last : 4) : 0;
@@ -518,9 +599,9 @@ __device__ __forceinline__ void voxel_mc_sums(const LDS* L, const QbDev& c,
                 nll_sum += sample_nll<T, SE, LITERAL>(L, c, lik, oef, dbv);
             }
         }
-    }
-    if (FAST) {  // sum_d [0.5 sum_t r^2 + sum_t log sigma + T log sqrt(2 pi)] over this lane's draws
-        nll_sum = fmaf(0.5f, nll_sum, (float)n_lik * lik.log_s_sum);
+        if (FAST) {  // sum_d [0.5 sum_t r^2 + sum_t log sigma + T log sqrt(2 pi)] over this lane's draws
+            nll_sum = fmaf(0.5f, nll_sum, (float)n_lik * lik.log_s_sum);
+        }
     }
     // the prior's parameters are fetched and transformed only now: they are dead weight in
     // registers during the likelihood loop
@@ -536,7 +617,21 @@ __device__ __forceinline__ void voxel_mc_sums(const LDS* L, const QbDev& c,
         qk.i_so = rcpf_(q.e_so);
         qk.i_sd = rcpf_(q.e_sd);
         qk.i_bl = -(qk.i_so * qk.i_sd) * q.c;
-        kl_sum = kl_draws_fast(qk, prior, K, zk, seed, vox, part, n_kl);
+        if constexpr (LPV == 1) {
+            const float per_draw = (prior.s_o + prior.s_d) - q_s_sum;
+            float first = 0.0f, pair = 0.0f;
+#pragma unroll 1
+            for (int p = 0; p < QB_LANES_PER_VOXEL; ++p) {
+                n_kl = 0;
+                const float sw = kl_draws_fast<1>(qk, prior, K, zk, seed, vox, p, n_kl);
+                share_sum(p, fmaf(0.5f, sw, (float)n_kl * per_draw), first, pair);
+            }
+            __builtin_amdgcn_s_setprio(QB_PRIO_AFTER);
+            kl_sum = first + pair;
+            return;
+        } else {
+            kl_sum = kl_draws_fast(qk, prior, K, zk, seed, vox, part, n_kl);
+        }
     } else {
         for (int j = part; 2 * j < K; j += QB_LANES_PER_VOXEL) {
             float z[4];
@@ -570,8 +665,9 @@ __device__ __forceinline__ void voxel_mc_sums(const LDS* L, const QbDev& c,
 
 // Block-level reduction of the three masked sums into one double3 partial per workgroup.
 // red: LDS scratch of 3 * (blockDim.x / 64) doubles.
+// add: the slot already holds the partial of an earlier launch on the stream, which this one joins.
 __device__ __forceinline__ void block_partials(double* red, float s_nll, float s_kl, float s_m,
-                                               double* __restrict__ partials) {
+                                               double* __restrict__ partials, bool add = false) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     s_nll = wave_sum(s_nll);
     s_kl = wave_sum(s_kl);
@@ -585,6 +681,7 @@ __device__ __forceinline__ void block_partials(double* red, float s_nll, float s
     if (threadIdx.x < 3) {
         double a = 0.0;
         for (int w = 0; w < nw; ++w) a += red[3 * w + threadIdx.x];
+        if (add) a += partials[3 * blockIdx.x + threadIdx.x];
         partials[3 * blockIdx.x + threadIdx.x] = a;
     }
 }
