@@ -5,10 +5,16 @@
 // tfa.optimizers.AdamW; TensorFlow autodiff through create_encoder (model.py:122-223) for voxel
 // batches (3x3x1 convolutions = their centre tap).
 //
-// Unlike the inference kernels these are plain row-major [N][64] float32 GEMMs on the exact-f32
-// matrix instruction (v_mfma_f32_16x16x4_f32), one layer per launch, activations saved to HBM:
-// training steps are 190-256 k voxels in the reference (train.py:68,103), ~1 GB of activations,
-// and HBM-bound at a few ms per step -- off the voxel-ELBO headline path, correctness first.
+// Activations are row-major [N][64] float32 tensors saved to HBM (training steps are 190-256 k voxels in the
+// reference, train.py:68,103: ~1 GB of activations, HBM-bound at a few ms per step).  The file holds, in this order:
+//   - the layer-wise GEMMs on the exact-f32 matrix instruction (v_mfma_f32_16x16x4_f32): the general xw_kernel, and
+//     the six kernels of the LDS-resident shapes (xw64_kernel and its heads / fork / dual / gate forms here,
+//     gate_bwd_wg_kernel further down), all written on the 16-voxel tile skeleton in front of xw64_kernel;
+//   - the 3x3x1 convolutions of crop batches in one launch (conv9_kernel, and conv9h_kernel on split-f16 operands);
+//   - the weight gradients (xtd*, their slab reductions) and the element-wise gate, norm and dropout kernels;
+//   - a gated block's whole backward in one or two launches (block_bwd_kernel, block_bwd_dw_kernel);
+//   - Launcher, which picks among them by shape, alignment and the context's selection bits, the forward and
+//     backward drivers behind the C ABI, the pre-training loss gradient and AdamW.
 #include <cmath>
 
 #include "canon_layout.h"
@@ -336,10 +342,137 @@ __global__ __launch_bounds__(256) void xw_kernel(const float* __restrict__ X, in
     }
 }
 
-// The common shape of xw_kernel as a leaner kernel: kdim, ndim <= 64, 16-byte aligned rows on both sides, no
-// gather.  Same staging and k / column permutations; ACCUM / MASK are compile-time, and the rows of Y and of
-// the mask that the epilogue needs are requested BEFORE the tile's 64 MFMAs (read right before their use
-// they cost four dependent memory latencies per tile -- half of the backward launches accumulate or mask).
+// ---- the 16-voxel tile skeleton of the 64-wide exact-f32 GEMM kernels --------------------------------------------
+// xw64_kernel, xw64_heads_kernel, xw64_fork_kernel, xw64_dual_kernel, xw64_gate_kernel and gate_bwd_wg_kernel are the
+// common shape of xw_kernel (kdim, ndim <= 64, 16-byte aligned rows on both sides, no gather) with different work
+// around the product.  What they share lives here: a workgroup of four waves stages W[k][j] in LDS (stage_w64); a
+// wave takes 16-voxel tiles (Tile16), reads its rows as float4 one tile ahead (fetch_rows under tile_loop), runs the
+// 64 MFMAs (mfma_rows) and writes four consecutive columns of four rows per lane (out_row, store_cols).  Rows of other
+// tensors that a kernel's epilogue needs are requested BEFORE the tile's MFMAs, at clamp_row's address (read right
+// before their use they cost four dependent memory latencies per tile).  Every address a helper forms is clamped, not
+// skipped: a lane beyond N or ntile reads the last row and stores nothing.
+struct Tile16 {
+    int lane, wave, g, i;   // lane (i, g) supplies voxel i, k = 16 q + 4 g + c, and receives voxels 4 g + r
+    int j;                  // its four output columns: j .. j + 3 (tile m of lane i = column 4 i + m)
+    int nq;                 // float4 per input row and lane: kdim rounded up to 16, over 16
+    int64_t N, ntile, first, stride;
+};
+__device__ __forceinline__ Tile16 make_tile16(int kdim, int64_t N, int waves) {
+    Tile16 t;
+    t.lane = threadIdx.x & 63, t.wave = threadIdx.x >> 6;
+    t.g = t.lane >> 4, t.i = t.lane & 15;
+    t.j = 4 * t.i;
+    t.nq = (kdim + 15) >> 4;
+    t.N = N, t.ntile = (N + 15) / 16;
+    t.first = (int64_t)blockIdx.x * waves + t.wave, t.stride = (int64_t)gridDim.x * waves;
+    return t;
+}
+// SLABS weight matrices Wl[s][k][j] = at(s, k, j) for k < kdim, j < ndim, zero up to [kpad][64], every load of every
+// slab in flight together (stage_in_flight); at() is only asked for elements inside the matrix.  Columns are permuted
+// to the float4 output layout, or left in place (`compact`: at most 16 columns, lane i = column i of tile 0).
+template <int SLABS = 1, class At>
+__device__ __forceinline__ void stage_w64(float* Wl, int kdim, int ndim, At at, bool compact = false) {
+    const int kpad = (kdim + 15) & ~15;
+    stage_in_flight<256>(
+        SLABS * kpad * 64,
+        [&](int e) {
+            const int s = SLABS > 1 && e >= kpad * 64, ee = s ? e - kpad * 64 : e;
+            return at(s, clamp_hi(ee >> 6, kdim), clamp_hi(ee & 63, ndim));
+        },
+        [&](int e, float v) {
+            const int s = SLABS > 1 && e >= kpad * 64, ee = s ? e - kpad * 64 : e;
+            const int k = ee >> 6, j = ee & 63;
+            (s ? Wl + kpad * kWs : Wl)[k * kWs + (compact ? j : 16 * (j & 3) + (j >> 2))] = k < kdim && j < ndim ? v : 0.0f;
+        });
+    __syncthreads();
+}
+__device__ __forceinline__ void bias4(const float* __restrict__ b, int j, int ndim, float (&bj)[4]) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) bj[m] = (b && j + m < ndim) ? b[j + m] : 0.0f;
+}
+// the voxel whose row this lane supplies to the product of `tile`, tile and voxel clamped into the tensor
+__device__ __forceinline__ int64_t in_row(const Tile16& t, int64_t tile) {
+    const int64_t tt = tile < t.ntile ? tile : t.ntile - 1;
+    return tt * 16 + t.i < t.N ? tt * 16 + t.i : t.N - 1;
+}
+// this lane's float4s of that row of X
+__device__ __forceinline__ void fetch_rows(const float* __restrict__ X, int ld, const Tile16& t, int64_t tile,
+                                           float4 (&rows)[4]) {
+    const float* xr = X + in_row(t, tile) * ld + 4 * t.g;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (q < t.nq) rows[q] = *reinterpret_cast<const float4*>(xr + 16 * q);
+}
+struct Rows16 {
+    float4 q[4];
+};
+// A wave's tiles with the next tile's rows in flight during this one: fetch(tile, rows) as fetch_rows, body(v0, rows)
+template <class Rows, class Fetch, class Body>
+__device__ __forceinline__ void tile_loop(const Tile16& t, Fetch fetch, Body body) {
+    Rows nxt;
+    int64_t tile = t.first;
+    if (tile < t.ntile) fetch(tile, nxt);
+    for (; tile < t.ntile; tile += t.stride) {
+        const Rows cur = nxt;
+        fetch(tile + t.stride, nxt);
+        body(tile * 16, cur);
+    }
+}
+template <class Body>
+__device__ __forceinline__ void tile_loop(const Tile16& t, const float* __restrict__ X, int ld, Body body) {
+    tile_loop<Rows16>(
+        t, [&](int64_t tile, Rows16& w) { fetch_rows(X, ld, t, tile, w.q); },
+        [&](int64_t v0, const Rows16& cur) { body(v0, cur.q); });
+}
+// acc[m] += a[c] (x) Ws[16 q + 4 g + c][tile m], c = 0 .. 3: the 16 MFMAs (`one`: the 4 of tile 0) of one float4
+__device__ __forceinline__ void mfma_quad(const Tile16& t, int q, const float (&a)[4], const float* Ws, f32x4 (&acc)[4],
+                                          bool one = false) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float* wr = Ws + (16 * q + 4 * t.g + c) * kWs + t.i;
+        if (one) {
+            acc[0] = QB_MFMA16F(a[c], wr[0], acc[0]);
+            continue;
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m) acc[m] = QB_MFMA16F(a[c], wr[16 * m], acc[m]);
+    }
+}
+// acc += rows (columns < kdim, through a relu if relu_in) . Ws
+__device__ __forceinline__ void mfma_rows(const Tile16& t, int kdim, const float4 (&cur)[4], const float* Ws,
+                                          f32x4 (&acc)[4], bool relu_in, bool one = false) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (q >= t.nq) break;
+        const int k0 = 16 * q + 4 * t.g;
+        float ac[4] = {k0 + 0 < kdim ? cur[q].x : 0.0f, k0 + 1 < kdim ? cur[q].y : 0.0f,
+                       k0 + 2 < kdim ? cur[q].z : 0.0f, k0 + 3 < kdim ? cur[q].w : 0.0f};
+        if (relu_in) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) ac[c] = fmaxf(ac[c], 0.0f);
+        }
+        mfma_quad(t, q, ac, Ws, acc, one);
+    }
+}
+// output row r of the tile at v0: its voxel, and the same clamped into the tensor for loads ahead of the MFMAs
+__device__ __forceinline__ int64_t out_row(const Tile16& t, int64_t v0, int r) { return v0 + 4 * t.g + r; }
+__device__ __forceinline__ int64_t clamp_row(const Tile16& t, int64_t v0, int r) {
+    return out_row(t, v0, r) < t.N ? out_row(t, v0, r) : t.N - 1;
+}
+__device__ __forceinline__ const float4& row4(const float* __restrict__ P, int64_t v, int ld, int j) {
+    return *reinterpret_cast<const float4*>(P + v * ld + j);
+}
+// columns j .. j + 3 of row v: one float4, or the ragged last columns one by one
+__device__ __forceinline__ void store_cols(float* __restrict__ Y, int ld, int64_t v, int j, int ndim, const float (&y)[4]) {
+    if (j + 3 < ndim) {
+        *reinterpret_cast<float4*>(Y + v * ld + j) = make_float4(y[0], y[1], y[2], y[3]);
+    } else {
+        for (int m = 0; m < 4 && j + m < ndim; ++m) Y[v * ld + j + m] = y[m];
+    }
+}
+
+// Y = act(X W + b) (+ Y) (* (mask > 0)), trans as xw_kernel; ACCUM / MASK are compile-time (half of the backward
+// launches accumulate or mask).
 template <bool ACCUM, bool MASK>
 __global__ __launch_bounds__(256) void xw64_kernel(const float* __restrict__ X, int ldx, int kdim,
                                                    const float* __restrict__ W, int ldw, int trans,
@@ -347,75 +480,25 @@ __global__ __launch_bounds__(256) void xw64_kernel(const float* __restrict__ X, 
                                                    int ndim, int act, const float* __restrict__ mask, int ldm,
                                                    int64_t N) {
     extern __shared__ float Wl[];
-    const int kpad = (kdim + 15) & ~15;
-    stage_in_flight<256>(
-        kpad * 64,
-        [&](int e) {
-            const int k = clamp_hi(e >> 6, kdim), j = clamp_hi(e & 63, ndim);
-            return trans ? W[j * ldw + k] : W[k * ldw + j];
-        },
-        [&](int e, float v) {
-            const int k = e >> 6, j = e & 63;
-            Wl[k * kWs + 16 * (j & 3) + (j >> 2)] = k < kdim && j < ndim ? v : 0.0f;   // tile m of lane i = column 4 i + m
-        });
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, i = lane & 15;
-    const int64_t ntile = (N + 15) / 16;
-    const int nq = (kdim + 15) >> 4;
-    const int j = 4 * i;
+    stage_w64(Wl, kdim, ndim, [&](int, int k, int j) { return trans ? W[j * ldw + k] : W[k * ldw + j]; });
+    const Tile16 t = make_tile16(kdim, N, 4);
+    const int j = t.j;
     float bj[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) bj[m] = (b && j + m < ndim) ? b[j + m] : 0.0f;
-    float4 nxt[4];
-    auto fetch = [&](int64_t tile) {
-        const int64_t t = tile < ntile ? tile : ntile - 1;
-        const int64_t v = t * 16 + i < N ? t * 16 + i : N - 1;
-        const float* xr = X + v * ldx + 4 * g;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (q < nq) nxt[q] = *reinterpret_cast<const float4*>(xr + 16 * q);
-    };
-    const int64_t stride = (int64_t)gridDim.x * 4;
-    int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-    if (tile < ntile) fetch(tile);
-    for (; tile < ntile; tile += stride) {
-        const int64_t v0 = tile * 16;
-        float4 cur[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
-        fetch(tile + stride);
+    bias4(b, j, ndim, bj);
+    tile_loop(t, X, ldx, [&](int64_t v0, const float4 (&cur)[4]) {
         float4 old[4], mk[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int64_t v = v0 + 4 * g + r < N ? v0 + 4 * g + r : N - 1;
-            if (ACCUM) old[r] = *reinterpret_cast<const float4*>(Y + v * ldy + j);
-            if (MASK) mk[r] = *reinterpret_cast<const float4*>(mask + v * ldm + j);
+            const int64_t v = clamp_row(t, v0, r);
+            if (ACCUM) old[r] = row4(Y, v, ldy, j);
+            if (MASK) mk[r] = row4(mask, v, ldm, j);
         }
-        f32x4 acc[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (q >= nq) break;
-            const int k0 = 16 * q + 4 * g;
-            float ac[4] = {k0 + 0 < kdim ? cur[q].x : 0.0f, k0 + 1 < kdim ? cur[q].y : 0.0f,
-                           k0 + 2 < kdim ? cur[q].z : 0.0f, k0 + 3 < kdim ? cur[q].w : 0.0f};
-            if (act & ACT_RELU_IN) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) ac[c] = fmaxf(ac[c], 0.0f);
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float* wr = Wl + (k0 + c) * kWs + i;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[m] = QB_MFMA16F(ac[c], wr[16 * m], acc[m]);
-            }
-        }
-        if (j >= ndim) continue;
+        f32x4 acc[4] = {};
+        mfma_rows(t, kdim, cur, Wl, acc, act & ACT_RELU_IN);
+        if (j >= ndim) return;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int64_t v = v0 + 4 * g + r;
+            const int64_t v = out_row(t, v0, r);
             if (v >= N) continue;
             float y[4];
 #pragma unroll
@@ -431,17 +514,15 @@ __global__ __launch_bounds__(256) void xw64_kernel(const float* __restrict__ X, 
                 y[0] = mk[r].x > 0.0f ? y[0] : 0.0f; y[1] = mk[r].y > 0.0f ? y[1] : 0.0f;
                 y[2] = mk[r].z > 0.0f ? y[2] : 0.0f; y[3] = mk[r].w > 0.0f ? y[3] : 0.0f;
             }
-            if (j + 3 < ndim) {
-                *reinterpret_cast<float4*>(Y + v * ldy + j) = make_float4(y[0], y[1], y[2], y[3]);
-            } else {  // ragged last columns
-                for (int m = 0; m < 4 && j + m < ndim; ++m) Y[v * ldy + j + m] = y[m];
-            }
+            store_cols(Y, ldy, v, j, ndim, y);
         }
-    }
+    });
 }
 
 // Both heads from one pass over the last activation rows, written straight into the caller's compact
 // [N][5] and [N][T] buffers: columns 0-4 of the stacked product are the q head, 5 .. 5 + T - 1 the log-sigma head.
+// With at most 16 columns (T <= 11) they all sit in tile 0, lane i = column i: one MFMA per k step instead of four,
+// and every lane has a column to store.
 __global__ __launch_bounds__(256) void xw64_heads_kernel(const float* __restrict__ X, int ld, int kdim,
                                                          const float* __restrict__ Wf, const float* __restrict__ bf,
                                                          const float* __restrict__ Ws, const float* __restrict__ bs,
@@ -450,85 +531,33 @@ __global__ __launch_bounds__(256) void xw64_heads_kernel(const float* __restrict
     extern __shared__ float Wl[];
     const int ndim = 5 + T;
     const bool compact = ndim <= 16;
-    const int kpad = (kdim + 15) & ~15;
-    stage_in_flight<256>(
-        kpad * 64,
-        [&](int e) {
-            const int k = clamp_hi(e >> 6, kdim), j = clamp_hi(e & 63, ndim);
+    stage_w64(
+        Wl, kdim, ndim,
+        [&](int, int k, int j) {
             const float* src = j < 5 ? Wf + k * 5 + j : Ws + k * T + (j - 5);
             return *src;
         },
-        [&](int e, float v) {
-            const int k = e >> 6, j = e & 63;
-            // tile m of lane i = column 4 i + m; with at most 16 columns (T <= 11) they all sit in tile 0, lane i = column i:
-            // one MFMA per k step instead of four, and every lane has a column to store
-            Wl[k * kWs + (compact ? j : 16 * (j & 3) + (j >> 2))] = k < kdim && j < ndim ? v : 0.0f;
-        });
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, i = lane & 15;
-    const int64_t ntile = (N + 15) / 16;
-    const int nq = (kdim + 15) >> 4;
-    const int j = 4 * i;
+        compact);
+    const Tile16 t = make_tile16(kdim, N, 4);
+    const int i = t.i, j = t.j;
     float bj[4];
 #pragma unroll
     for (int m = 0; m < 4; ++m) bj[m] = j + m < 5 ? bf[j + m] : (j + m < ndim ? bs[j + m - 5] : 0.0f);
     const float bi = i < 5 ? bf[i] : (i < ndim ? bs[i - 5] : 0.0f);   // compact: this lane's one column
-    float4 nxt[4];
-    auto fetch = [&](int64_t tile) {
-        const int64_t t = tile < ntile ? tile : ntile - 1;
-        const int64_t v = t * 16 + i < N ? t * 16 + i : N - 1;
-        const float* xr = X + v * ld + 4 * g;
+    tile_loop(t, X, ld, [&](int64_t v0, const float4 (&cur)[4]) {
+        f32x4 acc[4] = {};
+        mfma_rows(t, kdim, cur, Wl, acc, false, compact);
+        if (compact ? i >= ndim : j >= ndim) return;
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (q < nq) nxt[q] = *reinterpret_cast<const float4*>(xr + 16 * q);
-    };
-    const int64_t stride = (int64_t)gridDim.x * 4;
-    int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-    if (tile < ntile) fetch(tile);
-    for (; tile < ntile; tile += stride) {
-        const int64_t v0 = tile * 16;
-        float4 cur[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
-        fetch(tile + stride);
-        f32x4 acc[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (q >= nq) break;
-            const int k0 = 16 * q + 4 * g;
-            const float ac[4] = {k0 + 0 < kdim ? cur[q].x : 0.0f, k0 + 1 < kdim ? cur[q].y : 0.0f,
-                                 k0 + 2 < kdim ? cur[q].z : 0.0f, k0 + 3 < kdim ? cur[q].w : 0.0f};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float* wr = Wl + (k0 + c) * kWs + i;
-                if (compact) {
-                    acc[0] = QB_MFMA16F(ac[c], wr[0], acc[0]);
-                    continue;
-                }
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[m] = QB_MFMA16F(ac[c], wr[16 * m], acc[m]);
-            }
-        }
-        if (compact) {
-            if (i >= ndim) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t v = v0 + 4 * g + r;
-                if (v >= N) continue;
+        for (int r = 0; r < 4; ++r) {
+            const int64_t v = out_row(t, v0, r);
+            if (v >= N) continue;
+            if (compact) {
                 const float y = acc[0][r] + bi;
                 if (i < 5) out_q[v * 5 + i] = y;
                 else out_ls[v * T + (i - 5)] = y;
+                continue;
             }
-            continue;
-        }
-        if (j >= ndim) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int64_t v = v0 + 4 * g + r;
-            if (v >= N) continue;
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const int col = j + m;
@@ -537,7 +566,7 @@ __global__ __launch_bounds__(256) void xw64_heads_kernel(const float* __restrict
                 else if (col < ndim) out_ls[v * T + (col - 5)] = y;
             }
         }
-    }
+    });
 }
 
 // Forward of a residual block's two input branches in one pass over the input rows (voxel batches):
@@ -551,90 +580,30 @@ __global__ __launch_bounds__(256) void xw64_fork_kernel(const float* __restrict_
                                                         const float* __restrict__ b2, float* __restrict__ Y2,
                                                         int ldw, int64_t N) {
     extern __shared__ float Wl[];  // [2][kpad][kWs]
-    const int kpad = (kdim + 15) & ~15;
-    float* Wl2 = Wl + kpad * kWs;
-    stage_in_flight<256>(
-        2 * kpad * 64,
-        [&](int e) {
-            const int which = e >= kpad * 64, ee = which ? e - kpad * 64 : e;
-            const int k = clamp_hi(ee >> 6, kdim), j = clamp_hi(ee & 63, ndim);
-            return (which ? W2 : W1)[k * ldw + j];
-        },
-        [&](int e, float v) {
-            const int which = e >= kpad * 64, ee = which ? e - kpad * 64 : e;
-            const int k = ee >> 6, j = ee & 63;
-            (which ? Wl2 : Wl)[k * kWs + 16 * (j & 3) + (j >> 2)] = k < kdim && j < ndim ? v : 0.0f;
-        });
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, i = lane & 15;
-    const int64_t ntile = (N + 15) / 16;
-    const int nq = (kdim + 15) >> 4;
-    const int j = 4 * i;
+    stage_w64<2>(Wl, kdim, ndim, [&](int s, int k, int j) { return (s ? W2 : W1)[k * ldw + j]; });
+    const float* Wl2 = Wl + ((kdim + 15) & ~15) * kWs;
+    const Tile16 t = make_tile16(kdim, N, 4);
+    const int j = t.j;
     float bj1[4], bj2[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        bj1[m] = (b1 && j + m < ndim) ? b1[j + m] : 0.0f;
-        bj2[m] = (b2 && j + m < ndim) ? b2[j + m] : 0.0f;
-    }
-    float4 nxt[4];
-    auto fetch = [&](int64_t tile) {
-        const int64_t t = tile < ntile ? tile : ntile - 1;
-        const int64_t v = t * 16 + i < N ? t * 16 + i : N - 1;
-        const float* xr = X + v * ld + 4 * g;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (q < nq) nxt[q] = *reinterpret_cast<const float4*>(xr + 16 * q);
-    };
-    const int64_t stride = (int64_t)gridDim.x * 4;
-    int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-    if (tile < ntile) fetch(tile);
-    for (; tile < ntile; tile += stride) {
-        const int64_t v0 = tile * 16;
-        float4 cur[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
-        fetch(tile + stride);
+    bias4(b1, j, ndim, bj1);
+    bias4(b2, j, ndim, bj2);
+    tile_loop(t, X, ld, [&](int64_t v0, const float4 (&cur)[4]) {
 #pragma unroll
         for (int pass = 0; pass < 2; ++pass) {
-            const float* Ws = pass ? Wl2 : Wl;
-            f32x4 acc[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (q >= nq) break;
-                const int k0 = 16 * q + 4 * g;
-                float ac[4] = {k0 + 0 < kdim ? cur[q].x : 0.0f, k0 + 1 < kdim ? cur[q].y : 0.0f,
-                               k0 + 2 < kdim ? cur[q].z : 0.0f, k0 + 3 < kdim ? cur[q].w : 0.0f};
-                if (pass) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) ac[c] = fmaxf(ac[c], 0.0f);
-                }
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float* wr = Ws + (k0 + c) * kWs + i;
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) acc[m] = QB_MFMA16F(ac[c], wr[16 * m], acc[m]);
-                }
-            }
+            f32x4 acc[4] = {};
+            mfma_rows(t, kdim, cur, pass ? Wl2 : Wl, acc, pass);
             if (j >= ndim) continue;
-            float* Y = pass ? Y2 : Y1;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int64_t v = v0 + 4 * g + r;
+                const int64_t v = out_row(t, v0, r);
                 if (v >= N) continue;
                 float y[4];
 #pragma unroll
                 for (int m = 0; m < 4; ++m) y[m] = fmaxf(acc[m][r] + (pass ? bj2[m] : bj1[m]), 0.0f);
-                if (j + 3 < ndim) {
-                    *reinterpret_cast<float4*>(Y + v * ld + j) = make_float4(y[0], y[1], y[2], y[3]);
-                } else {
-                    for (int m = 0; m < 4 && j + m < ndim; ++m) Y[v * ld + j + m] = y[m];
-                }
+                store_cols(pass ? Y2 : Y1, ld, v, j, ndim, y);
             }
         }
-    }
+    });
 }
 
 // Backward-data of a residual block's two input branches in one pass (voxel batches):
@@ -646,94 +615,42 @@ __global__ __launch_bounds__(256) void xw64_dual_kernel(const float* __restrict_
                                                         const float* __restrict__ W2, int ld, int kdim, int ndim,
                                                         int ldw, float* __restrict__ Y, int64_t N) {
     extern __shared__ float Wl[];  // [2][kpad][kWs]
-    const int kpad = (kdim + 15) & ~15;
-    float* Wl2 = Wl + kpad * kWs;
-    stage_in_flight<256>(
-        2 * kpad * 64,
-        [&](int e) {
-            const int which = e >= kpad * 64, ee = which ? e - kpad * 64 : e;
-            const int k = clamp_hi(ee >> 6, kdim), j = clamp_hi(ee & 63, ndim);
-            return (which ? W2 : W1)[j * ldw + k];   // transposed: dX = dY W^T
+    stage_w64<2>(Wl, kdim, ndim, [&](int s, int k, int j) { return (s ? W2 : W1)[j * ldw + k]; });   // transposed: dX = dY W^T
+    const float* Wl2 = Wl + ((kdim + 15) & ~15) * kWs;
+    const Tile16 t = make_tile16(kdim, N, 4);
+    const int j = t.j;
+    struct Rows {
+        float4 x1[4], x2[4];
+    };
+    tile_loop<Rows>(
+        t,
+        [&](int64_t tile, Rows& w) {
+            fetch_rows(X1, ld, t, tile, w.x1);
+            fetch_rows(X2, ld, t, tile, w.x2);
         },
-        [&](int e, float v) {
-            const int which = e >= kpad * 64, ee = which ? e - kpad * 64 : e;
-            const int k = ee >> 6, j = ee & 63;
-            (which ? Wl2 : Wl)[k * kWs + 16 * (j & 3) + (j >> 2)] = k < kdim && j < ndim ? v : 0.0f;
+        [&](int64_t v0, const Rows& cur) {
+            float4 mk[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mk[r] = row4(M, clamp_row(t, v0, r), ld, j);
+            f32x4 acc[4] = {};
+            mfma_rows(t, kdim, cur.x1, Wl, acc, false);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {   // through the relu of the first branch, before the second one is added
+                acc[0][r] = mk[r].x > 0.0f ? acc[0][r] : 0.0f;
+                acc[1][r] = mk[r].y > 0.0f ? acc[1][r] : 0.0f;
+                acc[2][r] = mk[r].z > 0.0f ? acc[2][r] : 0.0f;
+                acc[3][r] = mk[r].w > 0.0f ? acc[3][r] : 0.0f;
+            }
+            mfma_rows(t, kdim, cur.x2, Wl2, acc, false);
+            if (j >= ndim) return;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t v = out_row(t, v0, r);
+                if (v >= N) continue;
+                const float y[4] = {acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+                store_cols(Y, ld, v, j, ndim, y);
+            }
         });
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, i = lane & 15;
-    const int64_t ntile = (N + 15) / 16;
-    const int nq = (kdim + 15) >> 4;
-    const int j = 4 * i;
-    float4 n1[4], n2[4];
-    auto fetch = [&](int64_t tile) {
-        const int64_t t = tile < ntile ? tile : ntile - 1;
-        const int64_t v = t * 16 + i < N ? t * 16 + i : N - 1;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (q < nq) {
-                n1[q] = *reinterpret_cast<const float4*>(X1 + v * ld + 4 * g + 16 * q);
-                n2[q] = *reinterpret_cast<const float4*>(X2 + v * ld + 4 * g + 16 * q);
-            }
-    };
-    auto chain = [&](const float4 (&cur)[4], const float* Ws, f32x4 (&acc)[4]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (q >= nq) break;
-            const int k0 = 16 * q + 4 * g;
-            const float ac[4] = {k0 + 0 < kdim ? cur[q].x : 0.0f, k0 + 1 < kdim ? cur[q].y : 0.0f,
-                                 k0 + 2 < kdim ? cur[q].z : 0.0f, k0 + 3 < kdim ? cur[q].w : 0.0f};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float* wr = Ws + (k0 + c) * kWs + i;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[m] = QB_MFMA16F(ac[c], wr[16 * m], acc[m]);
-            }
-        }
-    };
-    const int64_t stride = (int64_t)gridDim.x * 4;
-    int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-    if (tile < ntile) fetch(tile);
-    for (; tile < ntile; tile += stride) {
-        const int64_t v0 = tile * 16;
-        float4 c1[4], c2[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            c1[q] = n1[q];
-            c2[q] = n2[q];
-        }
-        fetch(tile + stride);
-        float4 mk[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int64_t v = v0 + 4 * g + r < N ? v0 + 4 * g + r : N - 1;
-            mk[r] = *reinterpret_cast<const float4*>(M + v * ld + j);
-        }
-        f32x4 acc[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        chain(c1, Wl, acc);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {   // through the relu of the first branch, before the second one is added
-            acc[0][r] = mk[r].x > 0.0f ? acc[0][r] : 0.0f;
-            acc[1][r] = mk[r].y > 0.0f ? acc[1][r] : 0.0f;
-            acc[2][r] = mk[r].z > 0.0f ? acc[2][r] : 0.0f;
-            acc[3][r] = mk[r].w > 0.0f ? acc[3][r] : 0.0f;
-        }
-        chain(c2, Wl2, acc);
-        if (j >= ndim) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int64_t v = v0 + 4 * g + r;
-            if (v >= N) continue;
-            if (j + 3 < ndim) {
-                *reinterpret_cast<float4*>(Y + v * ld + j) = make_float4(acc[0][r], acc[1][r], acc[2][r], acc[3][r]);
-            } else {
-                for (int m = 0; m < 4 && j + m < ndim; ++m) Y[v * ld + j + m] = acc[m][r];
-            }
-        }
-    }
 }
 
 // The gating layer of a residual block with its blend as the epilogue (channel-wise gating, model.py:164-170):
@@ -747,70 +664,24 @@ __global__ __launch_bounds__(256) void xw64_gate_kernel(const float* __restrict_
                                                         const float* __restrict__ skip, float* __restrict__ bout,
                                                         int ldy, int ndim, float offset, int64_t N) {
     extern __shared__ float Wl[];
-    const int kpad = (kdim + 15) & ~15;
-    stage_in_flight<256>(
-        kpad * 64,
-        [&](int e) {
-            const int k = clamp_hi(e >> 6, kdim), j = clamp_hi(e & 63, ndim);
-            return W[k * ldw + j];
-        },
-        [&](int e, float v) {
-            const int k = e >> 6, j = e & 63;
-            Wl[k * kWs + 16 * (j & 3) + (j >> 2)] = k < kdim && j < ndim ? v : 0.0f;   // tile m of lane i = column 4 i + m
-        });
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, i = lane & 15;
-    const int64_t ntile = (N + 15) / 16;
-    const int nq = (kdim + 15) >> 4;
-    const int j = 4 * i;
+    stage_w64(Wl, kdim, ndim, [&](int, int k, int j) { return W[k * ldw + j]; });
+    const Tile16 t = make_tile16(kdim, N, 4);
+    const int j = t.j;
     float bj[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) bj[m] = (b && j + m < ndim) ? b[j + m] : 0.0f;
-    float4 nxt[4];
-    auto fetch = [&](int64_t tile) {
-        const int64_t t = tile < ntile ? tile : ntile - 1;
-        const int64_t v = t * 16 + i < N ? t * 16 + i : N - 1;
-        const float* xr = X + v * ldx + 4 * g;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (q < nq) nxt[q] = *reinterpret_cast<const float4*>(xr + 16 * q);
-    };
-    const int64_t stride = (int64_t)gridDim.x * 4;
-    int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-    if (tile < ntile) fetch(tile);
-    for (; tile < ntile; tile += stride) {
-        const int64_t v0 = tile * 16;
-        float4 cur[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
-        fetch(tile + stride);
+    bias4(b, j, ndim, bj);
+    tile_loop(t, X, ldx, [&](int64_t v0, const float4 (&cur)[4]) {
         float4 sk[4], rr[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int64_t v = v0 + 4 * g + r < N ? v0 + 4 * g + r : N - 1;
-            sk[r] = *reinterpret_cast<const float4*>(skip + v * ldy + j);
-            rr[r] = *reinterpret_cast<const float4*>(X + v * ldx + j);
+            const int64_t v = clamp_row(t, v0, r);
+            sk[r] = row4(skip, v, ldy, j);
+            rr[r] = row4(X, v, ldx, j);
         }
-        f32x4 acc[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (q >= nq) break;
-            const int k0 = 16 * q + 4 * g;
-            const float ac[4] = {k0 + 0 < kdim ? cur[q].x : 0.0f, k0 + 1 < kdim ? cur[q].y : 0.0f,
-                                 k0 + 2 < kdim ? cur[q].z : 0.0f, k0 + 3 < kdim ? cur[q].w : 0.0f};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float* wr = Wl + (k0 + c) * kWs + i;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[m] = QB_MFMA16F(ac[c], wr[16 * m], acc[m]);
-            }
-        }
+        f32x4 acc[4] = {};
+        mfma_rows(t, kdim, cur, Wl, acc, false);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int64_t v = v0 + 4 * g + r;
+            const int64_t v = out_row(t, v0, r);
             if (v >= N) continue;
             const float s4[4] = {sk[r].x, sk[r].y, sk[r].z, sk[r].w}, r4[4] = {rr[r].x, rr[r].y, rr[r].z, rr[r].w};
             float gl[4], o[4];
@@ -821,13 +692,9 @@ __global__ __launch_bounds__(256) void xw64_gate_kernel(const float* __restrict_
                 o[m] = j + m < ndim ? s4[m] * (1.0f - gate) + r4[m] * gate : 0.0f;   // zero beyond U, as gate_fwd_kernel
             }
             *reinterpret_cast<float4*>(bout + v * ldy + j) = make_float4(o[0], o[1], o[2], o[3]);
-            if (j + 3 < ndim) {
-                *reinterpret_cast<float4*>(GL + v * ldy + j) = make_float4(gl[0], gl[1], gl[2], gl[3]);
-            } else {
-                for (int m = 0; m < 4 && j + m < ndim; ++m) GL[v * ldy + j + m] = gl[m];
-            }
+            store_cols(GL, ldy, v, j, ndim, gl);
         }
-    }
+    });
 }
 
 // The whole 3x3x1 'same' convolution of one layer in ONE launch (U <= 64):
@@ -2177,11 +2044,12 @@ __global__ void gate_bwd_kernel(const float* __restrict__ d_b, const float* __re
 
 // gate_bwd_kernel and the gating conv's backward-data product in one launch, for channel-wise gates on [N][64] rows
 // (U = G <= 64, U % 4 == 0): the crop backward's first two kernels read d b, gl, skip, r and wrote d s', d r, d gl,
-// then re-read d gl and d r to add d gl Wg^T -- ten tensor passes, here seven.  A wave takes 16 voxels.  In the
-// product's INPUT layout (lane (i, g): voxel i, units 16 q + 4 g ..) it forms d gl and d s' from the four rows and
-// stores them; d gl feeds the 64 exact-f32 MFMAs of xw64_kernel as it is formed.  d r = d b g + d gl Wg^T leaves in the
-// product's OUTPUT layout (lane (i, g): voxels 4 g + r, units 4 i ..), where d b and gl are read a second time (the
-// rows the tile just brought in: cache hits) and the gate evaluated again -- requested before the MFMAs.
+// then re-read d gl and d r to add d gl Wg^T -- ten tensor passes, here seven.  A wave takes 16 voxels (the tile
+// skeleton beside xw64_kernel).  In the product's INPUT layout (lane (i, g): voxel i, units 16 q + 4 g ..) it forms
+// d gl and d s' from the four rows and stores them; d gl feeds the 64 exact-f32 MFMAs of xw64_kernel as it is formed.
+// d r = d b g + d gl Wg^T leaves in the product's OUTPUT layout (lane (i, g): voxels 4 g + r, units 4 i ..), where d b
+// and gl are read a second time (the rows the tile just brought in: cache hits) and the gate evaluated again --
+// requested before the MFMAs.
 __global__ __launch_bounds__(256) void gate_bwd_wg_kernel(const float* __restrict__ d_b, const float* __restrict__ gl,
                                                           const float* __restrict__ skip, const float* __restrict__ r,
                                                           const float* __restrict__ Wg, float* __restrict__ d_skip_pre,
@@ -2189,30 +2057,14 @@ __global__ __launch_bounds__(256) void gate_bwd_wg_kernel(const float* __restric
                                                           float offset, int U, int64_t N) {
     extern __shared__ float Wl[];
     constexpr int ld = kLd;
-    const int kpad = (U + 15) & ~15;
-    stage_in_flight<256>(
-        kpad * 64,
-        [&](int e) {   // Wl[k][j] = Wg[j][k]: d r = d gl Wg^T
-            const int k = clamp_hi(e >> 6, U), j = clamp_hi(e & 63, U);
-            return Wg[j * U + k];
-        },
-        [&](int e, float v) {
-            const int k = e >> 6, j = e & 63;
-            Wl[k * kWs + 16 * (j & 3) + (j >> 2)] = k < U && j < U ? v : 0.0f;   // tile m of lane i = column 4 i + m
-        });
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, i = lane & 15;
-    const int64_t ntile = (N + 15) / 16;
-    const int nq = (U + 15) >> 4;
-    const int j = 4 * i;
+    stage_w64(Wl, U, U, [&](int, int k, int j) { return Wg[j * U + k]; });   // Wl[k][j] = Wg[j][k]: d r = d gl Wg^T
+    const Tile16 t = make_tile16(U, N, 4);
+    const int g = t.g, i = t.i, j = t.j, nq = t.nq;
     struct Rows {
         float4 db[4], gl[4], sk[4], r[4];
     };
     auto fetch = [&](int64_t tile, Rows& w) {
-        const int64_t t = tile < ntile ? tile : ntile - 1;
-        const int64_t v = t * 16 + i < N ? t * 16 + i : N - 1;
-        const int64_t o = v * ld + 4 * g;
+        const int64_t o = in_row(t, tile) * ld + 4 * g;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             if (q < nq) {
@@ -2224,22 +2076,19 @@ __global__ __launch_bounds__(256) void gate_bwd_wg_kernel(const float* __restric
     };
     // (no software prefetch of the next tile's rows: three waves per SIMD at 148 registers beat two at 196 with it,
     // 1.449 against 1.455 ms per crop step)
-    const int64_t stride = (int64_t)gridDim.x * 4;
-    for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < ntile; tile += stride) {
+    for (int64_t tile = t.first; tile < t.ntile; tile += t.stride) {
         const int64_t v0 = tile * 16;
         Rows cur;
         fetch(tile, cur);
         float4 odb[4], ogl[4];   // the output layout's rows of d b and gl
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
-            const int64_t v = v0 + 4 * g + rr < N ? v0 + 4 * g + rr : N - 1;
+            const int64_t v = clamp_row(t, v0, rr);
             const int jj = j < U ? j : 0;
-            odb[rr] = *reinterpret_cast<const float4*>(d_b + v * ld + jj);
-            ogl[rr] = *reinterpret_cast<const float4*>(gl + v * ld + jj);
+            odb[rr] = row4(d_b, v, ld, jj);
+            ogl[rr] = row4(gl, v, ld, jj);
         }
-        f32x4 acc[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        f32x4 acc[4] = {};
         const bool row_ok = v0 + i < N;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -2262,12 +2111,7 @@ __global__ __launch_bounds__(256) void gate_bwd_wg_kernel(const float* __restric
                 *reinterpret_cast<float4*>(d_gl + o) = make_float4(dgl[0], dgl[1], dgl[2], dgl[3]);
                 *reinterpret_cast<float4*>(d_skip_pre + o) = make_float4(ds[0], ds[1], ds[2], ds[3]);
             }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float* wr = Wl + (k0 + c) * kWs + i;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[m] = QB_MFMA16F(dgl[c], wr[16 * m], acc[m]);
-            }
+            mfma_quad(t, q, dgl, Wl, acc);
         }
         // padding units of the rows (U .. 63): zeros, as gate_bwd_kernel leaves them
         if (row_ok)
@@ -2278,7 +2122,7 @@ __global__ __launch_bounds__(256) void gate_bwd_wg_kernel(const float* __restric
             }
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
-            const int64_t v = v0 + 4 * g + rr;
+            const int64_t v = out_row(t, v0, rr);
             if (v >= N) continue;
             float y[4];
             const float db4[4] = {odb[rr].x, odb[rr].y, odb[rr].z, odb[rr].w};
@@ -2877,6 +2721,7 @@ struct Launcher {
         int64_t nb = (N + 63) / 64;
         int64_t cap = (int64_t)ctx->num_cus * 4;  // 256-thread blocks per CU; measured per 1 M-voxel step with the
                                                   // prefetching xw_kernel: 2 -> 8.4, 3 -> 7.6, 4 -> 7.3, 6 -> 7.7, 8 -> 7.4, 16 -> 7.5 ms
+                                                  // (the six kernels on the tile skeleton are launched on this grid too)
         return (int)(nb < cap ? (nb > 0 ? nb : 1) : cap);
     }
     // Y (row stride ldy) = act(X W + b); ndim output columns in slabs of 64
@@ -3350,7 +3195,6 @@ static int train_fwd_impl(const qbold_ctx* ctx, const qbold_encoder_shape* shape
     const int A_OUT = gelu ? ACT_GELU : ACT_RELU, A_IN = gelu ? ACT_GELU_IN : ACT_RELU_IN;
     k.xw(slot(0), ld, T, w + c.W0, U, 0, w + c.b0, slot(1), U, A_OUT, 0, nullptr);
     const float* cur = slot(1);
-    float* head = slot(2 + 5 * L);  // scratch slot for the head output
     if (stream_sel == 1) {
         for (int l = 0; l < L; ++l) {
             const float* wb = w + c.blk0 + l * c.blk_stride;
@@ -3428,7 +3272,6 @@ static int train_fwd_impl(const qbold_ctx* ctx, const qbold_encoder_shape* shape
         }
     }
     // heads straight into the caller's [N][5] / [N][T] buffers
-    (void)head;
     if (stream_sel == 2 && out_log_sigma && U <= 64 && ld == kLd && 5 + T <= 64 &&
         (reinterpret_cast<uintptr_t>(cur) & 15) == 0 && !(ctx->kernel_sel & 32768)) {
         hipLaunchKernelGGL(xw64_heads_kernel, dim3(k.grid()), dim3(256), sizeof(float) * 64 * kWs, k.s, cur, ld, U,
