@@ -266,6 +266,14 @@ class Oracle:
         del keep
         return o2, sg
 
+    def dropout_factors(self, rate, seed, layer, rows, U, row0=0):
+        """The keep factors [rows, U] (0 or 1 / (1 - thresh / 65536)) that normalizer `layer` (2 l + which) of a
+        training-mode forward at (rate, seed) applies to rows row0 .. row0 + rows - 1 (qbold_oracle.c: drop_factor)."""
+        out = np.empty((int(rows), int(U)), self.dtype)
+        self.lib.qbo_dropout_factors(C.c_double(rate), C.c_uint64(int(seed)), C.c_int(int(layer)), C.c_int64(int(row0)),
+                                     C.c_int64(int(rows)), C.c_int(int(U)), self._p(out))
+        return out
+
     def smoothness_loss(self, q, mask):
         """model.py:726-754 on q [B,X,Y,Z,5], mask [B,X,Y,Z]."""
         q = self._a(q)

@@ -548,16 +548,25 @@ void qbo_set_normalizer(const real *ln, double dropout_rate, uint64_t dropout_se
     g_drop_seed = dropout_seed;
 }
 void qbo_philox4x32_7(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
-static real drop_factor(int64_t row, int col, int layer) {
-    if (!(g_drop_rate > 0.0) || g_drop_seed == 0) return R(1.0);
-    double rate = g_drop_rate < 0.999 ? g_drop_rate : 0.999;
+static real drop_factor_of(double drop_rate, uint64_t seed, int64_t row, int col, int layer) {
+    if (!(drop_rate > 0.0) || seed == 0) return R(1.0);
+    double rate = drop_rate < 0.999 ? drop_rate : 0.999;
     uint32_t thresh = (uint32_t)lrintf((float)rate * 65536.0f);
     uint32_t ctr[4] = {(uint32_t)row, (uint32_t)((uint64_t)row >> 32), (uint32_t)(col >> 3) | ((uint32_t)layer << 16), 5u};
-    uint32_t key[2] = {(uint32_t)g_drop_seed, (uint32_t)(g_drop_seed >> 32)}, o[4];
+    uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)}, o[4];
     qbo_philox4x32_7(ctr, key, o);
     uint32_t w = o[(col >> 1) & 3];
     uint32_t hw = (col & 1) ? (w >> 16) : (w & 0xffffu);
     return hw < thresh ? R(0.0) : R(1.0 / (1.0 - (double)thresh / 65536.0));
+}
+static real drop_factor(int64_t row, int col, int layer) {
+    return drop_factor_of(g_drop_rate, g_drop_seed, row, col, layer);
+}
+/* the keep factors the normalizer of `layer` (2 l + which) applies to rows row0 .. row0 + rows - 1: out[rows][U], each 0
+ * or 1 / (1 - thresh / 65536) */
+void qbo_dropout_factors(double rate, uint64_t seed, int layer, int64_t row0, int64_t rows, int U, real *out) {
+    for (int64_t r = 0; r < rows; ++r)
+        for (int c = 0; c < U; ++c) out[r * U + c] = drop_factor_of(rate, seed, row0 + r, c, layer);
 }
 /* out = act(LN(Dropout(in))) for a [B][rows_per_b][U] tensor */
 static void normalizer(const real *in, real *out, int B, int64_t rows_per_b, int U, int layer, int l, int which) {

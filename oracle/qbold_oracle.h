@@ -78,6 +78,9 @@ void qbo_set_encoder_bf16(int on);
 /* test hook: add_normalizer (model.py:131-140) in qbo_encoder_fwd_spatial: GroupNormalization parameters ln [L][4][U]
  * (gamma1, beta1, gamma2, beta2 per block; NULL = off) and a training-mode dropout (rate, seed; seed 0 = inference) */
 void qbo_set_normalizer(const real *ln, double dropout_rate, uint64_t dropout_seed);
+/* the dropout keep factors of that stream (0 or 1 / (1 - thresh / 65536)) for normalizer `layer` (2 l + which), rows
+ * row0 .. row0 + rows - 1, columns 0 .. U - 1: out [rows][U] */
+void qbo_dropout_factors(double rate, uint64_t seed, int layer, int64_t row0, int64_t rows, int U, real *out);
 /* test hook: 'gelu' (Keras exact form) instead of 'relu' in the encoder restatements (model.py:60, 115-120) */
 void qbo_set_activation_gelu(int on);
 

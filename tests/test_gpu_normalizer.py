@@ -94,14 +94,29 @@ def test_layer_norm_forward_matches_oracle(ctx, oracle32, activation, geometry):
 def test_dropout_training_forward_matches_oracle_stream(ctx, oracle32, layer_norm):
     """A training state's forward draws the step's dropout mask from the library's Philox stream 5; the oracle
     regenerates the same mask from (rate, seed).  Inference is the identity (Keras)."""
+    _dropout_stream(ctx, oracle32, layer_norm, (2, 4, 3, 2), 16)
+
+
+@pytest.mark.parametrize("layer_norm", [False, True])
+def test_dropout_training_forward_matches_oracle_stream_wide(ctx, oracle32, layer_norm):
+    """The same at U = 200 on an (N,1,1,1) batch: the GPU's mask against the oracle's beyond column 16 (25 counter values
+    per row, the row kernels' four column iterations)."""
+    _dropout_stream(ctx, oracle32, layer_norm, (50, 1, 1, 1), 200)
+
+
+def _dropout_stream(ctx, oracle32, layer_norm, geometry, U):
     from qbold_vi_amd.ops import TrainState
-    B, X, Y, Z = 2, 4, 3, 2
+    B, X, Y, Z = geometry
     rate = 0.25
-    w, ln, ew = make(ctx, 16, 2, "relu", layer_norm=layer_norm, dropout_rate=rate)
+    w, ln, ew = make(ctx, U, 2, "relu", layer_norm=layer_norm, dropout_rate=rate)
     x = crop_batch(oracle32, B, X, Y, Z, seed=8)
     n = B * X * Y * Z
+
+    def fwd(state):    # the crop entry point is built for U <= 64; a wider (N,1,1,1) batch takes the voxel one
+        return state.forward_spatial(dev(x)) if U <= 64 else state.forward(dev(x.reshape(n, 11)), 2)
+
     st = TrainState(ctx, ew)            # training
-    q, ls = st.forward_spatial(dev(x))
+    q, ls = fwd(st)
     seed = int(ew.shape.dropout_seed)
     assert seed != 0
     q_want, _ = oracle32.encoder_fwd_spatial(w, x, ln=ln, dropout_rate=rate, dropout_seed=seed)
@@ -109,15 +124,20 @@ def test_dropout_training_forward_matches_oracle_stream(ctx, oracle32, layer_nor
     assert np.max(np.abs(q.cpu().numpy() - q_want.reshape(n, 5))) < 3e-5
     assert np.max(np.abs(q_want - q_inf)) > 1e-3            # the mask does something
     inf = TrainState(ctx, ew, optimiser_state=False)
-    qi, _ = inf.forward_spatial(dev(x))
+    qi, _ = fwd(inf)
     assert int(ew.shape.dropout_seed) == 0
     assert np.max(np.abs(qi.cpu().numpy() - q_inf.reshape(n, 5))) < 3e-5
     # another step, another mask
     st.step += 1
-    q2, _ = st.forward_spatial(dev(x))
+    q2, _ = fwd(st)
     assert int(ew.shape.dropout_seed) == seed + 1 and not torch.equal(q, q2)
-    # the drop rate is what was asked for: the share of zeros among the activations the first normalizer lets through
-    from oracle.oracle import Oracle  # noqa: F401  (the mask itself is restated in oracle/qbold_oracle.c: drop_factor)
+    # the drop rate is what was asked for: the share of zeros among the step's keep factors (the mask the forward above
+    # was compared under), within 4 binomial sigma of the threshold
+    p = float(np.rint(np.float32(rate) * np.float32(65536.0))) / 65536.0
+    f = np.stack([oracle32.dropout_factors(rate, seed, layer, n, U) for layer in range(4)])
+    assert np.all((f == 0.0) | (f == np.float32(1.0 / (1.0 - p))))
+    share = float((f == 0.0).mean())
+    assert abs(share - p) <= 4.0 * np.sqrt(p * (1.0 - p) / f.size), (share, p)
 
 
 def _perturbed(w, ln, direction, dln, eps):

@@ -42,18 +42,29 @@ def signals(oracle32, shape, seed):
 
 class Path:
     """One backward path: a context with a kernel selection, the weights, a batch (voxels [N, 11] or crops
-    [B, X, Y, Z, 11]) and the stream."""
+    [B, X, Y, Z, 11]) and the stream; optionally the activation, GroupNormalization parameters ln [L, 4, U]
+    (use_layer_norm) and a dropout rate, whose keep factors at the state's step come from `oracle`."""
 
-    def __init__(self, params, sel, w, x, stream=2):
+    act, ln, drop, seed = "relu", None, None, 0   # a plain relu path (a subclass with a constructor of its own keeps these)
+
+    def __init__(self, params, sel, w, x, stream=2, activation="relu", ln=None, dropout_rate=0.0, oracle=None):
         from qbold_vi_amd.ops import Context, EncoderWeights, TrainState
         self.ctx = Context(params, full_model=True, include_blood=True)
         self.ctx.set_kernel_selection(sel)
         U, L, cw = w["W0"].shape[1], w["Wc"].shape[0], w["Wg"].shape[2] > 1
-        self.ew = EncoderWeights(self.ctx, 11, U, L, cw, w["gate_offset"], spatial_taps=9).set_from_arrays(w)
+        self.ew = EncoderWeights(self.ctx, 11, U, L, cw, w["gate_offset"], spatial_taps=9, activation=activation,
+                                 layer_norm=ln is not None, dropout_rate=dropout_rate)
+        self.ew.set_from_arrays(w if ln is None else dict(w, ln=ln))
         self.st = TrainState(self.ctx, self.ew)
         self.w, self.x, self.stream, self.L = w, x, stream, L
         self.crops = x.ndim == 5
         self.n = x.size // 11
+        self.act, self.ln = activation, ln
+        if dropout_rate > 0.0:   # one forward draws the step's mask; every backward here runs at the same step
+            self.forward()
+            self.seed = int(self.ew.shape.dropout_seed)
+            assert self.seed != 0
+            self.drop = ref.drop_factors(oracle, dropout_rate, self.seed, L, self.n, U)
 
     def forward(self, x=None):
         x = self.x if x is None else x
@@ -63,6 +74,7 @@ class Path:
 
     def grad(self, g_q, g_ls, sums=None):
         self.forward()
+        assert int(self.ew.shape.dropout_seed) == self.seed
         s = None if sums is None else dev(np.array([0.0, 0.0, sums], np.float64))
         gq, gls = dev(g_q.astype(np.float32)), None if g_ls is None else dev(g_ls.astype(np.float32))
         if self.crops:
@@ -77,7 +89,8 @@ class Path:
 
     def reference(self, g_q, g_ls):
         """float64 VJP (no normaliser), the relu screen's reach per voxel and the bias bounds"""
-        grads, pre, babs = ref.vjp(self.w, self.x, g_q, g_ls, None, stream=self.stream, se_idx=2)
+        grads, pre, babs = ref.vjp(self.w, self.x, g_q, g_ls, None, stream=self.stream, se_idx=2, act=self.act,
+                                   ln=self.ln, drop=self.drop)
         return grads, ref.relu_sites_near_zero(pre), babs
 
     def screened(self, g_q, g_ls, min_keep=0.8):
