@@ -98,6 +98,9 @@ __global__ __launch_bounds__(kBlock) void elbo_bwd_kernel(
             const float m = mask ? mask[v] : 1.0f;
             qb::VoxelLik<T> lik;
             qb::prepare_lik<T, SE, true>(c, xv, lsv, m, lik);
+            // prepare_lik's normaliser of the data, and the tau of single-image normalisation on linear data (-1: none)
+            const float nt = qb::se_norm<T, SE>(c, xv), inv_nt = qb::rcpf_(nt);
+            const int se1 = c.predict_log ? -1 : SE >= 0 ? SE : c.multi_norm ? -1 : c.se_idx;
             const qb::LogitMvn qm = qb::make_mvn(qv), pm = qb::make_mvn(pv);
             const uint64_t vox = (uint64_t)(voxel0 + v);
 
@@ -129,7 +132,13 @@ __global__ __launch_bounds__(kBlock) void elbo_bwd_kernel(
                     float sig[T];
 #pragma unroll
                     for (int t = 0; t < T; ++t) sig[t] = qb::fwd_signal_fast(&L, c, fv, t);
-                    const float inv_np = qb::rcpf_(qb::se_norm<T, SE>(c, sig));
+                    const float np_ = qb::se_norm<T, SE>(c, sig), inv_np = qb::rcpf_(np_);
+                    // At the image that normalises, y = x / (x + 1e-3) and yhat = s / (s + 1e-3) are both within 1e-3
+                    // of 1 and float32 y - yhat is rounding below 1e-7; their difference is taken from the two
+                    // normalisers instead, 1e-3 (x - s) / ((x + 1e-3) (s + 1e-3)), which keeps its digits.  Only
+                    // d / d log sigma_t = 1 - r^2 takes it, the one output it decides (once sigma is ~1e-5: MEASUREMENTS.md
+                    // section 23); the value and the heads' path keep the forward kernels' r, bit for bit.
+                    const float d_se = (((1e-3f * (nt - np_)) * inv_nt) * inv_np);
                     float acc = 0.0f, a1 = 0.0f;
                     float gy[T];
 #pragma unroll
@@ -140,15 +149,17 @@ __global__ __launch_bounds__(kBlock) void elbo_bwd_kernel(
                             yp = m > 0.0f ? __logf(yp) : 0.0f;
                         }
                         const float r = (lik.yt[t] - yp) * lik.inv_s[t];
-                        float dr = r;                             // d nll_t / d r
+                        const float rg = t == se1 ? d_se * lik.inv_s[t] : r;   // r as d / d log sigma_t takes it
+                        float dr = r, drg = rg;                   // d nll_t / d r
                         if (c.use_student_t) {                    // -StudentT(df, 0, sigma).log_prob, :557-559
                             const float w = (c.st_df + 1.0f) * qb::rcpf_(fmaf(r, r, c.st_df));
                             acc += (c.st_df + 1.0f) * log1pf(r * r * qb::rcpf_(c.st_df)) - 2.0f * c.st_const;
                             dr = w * r;
+                            drg = (c.st_df + 1.0f) * qb::rcpf_(fmaf(rg, rg, c.st_df)) * rg;
                         } else {
                             acc = fmaf(r, r, acc);
                         }
-                        gls[t] += 1.0f - dr * r;                  // d/d log sigma_t of log sigma_t + nll_t(r)
+                        gls[t] += 1.0f - drg * rg;                // d/d log sigma_t of log sigma_t + nll_t(r)
                         gy[t] = -dr * lik.inv_s[t] * dyp;         // d nll / d yhat_t
                         a1 = fmaf(gy[t], sig[t], a1);
                     }
@@ -292,13 +303,11 @@ __global__ __launch_bounds__(kBlock) void elbo_bwd_kernel(
             if (part == 0) {
                 // transform_std / transform_offdiag (model.py:288-294): s = 3 tanh(raw) - 1,
                 // c = tanh(raw) e^-2.  NB the -(s_o + s_d)_q term of the KL is stop-gradient.
-                const float th1 = (qm.s_o + 1.0f) * (1.0f / 3.0f), th3 = (qm.s_d + 1.0f) * (1.0f / 3.0f);
-                const float th4 = qm.c * 7.38905609893065f;
                 g_q[v * 5 + 0] = g_mu_o;
-                g_q[v * 5 + 1] = g_so * 3.0f * (1.0f - th1 * th1);
+                g_q[v * 5 + 1] = g_so * 3.0f * qb::sech2f_(qv[1]);
                 g_q[v * 5 + 2] = g_mu_d;
-                g_q[v * 5 + 3] = g_sd * 3.0f * (1.0f - th3 * th3);
-                g_q[v * 5 + 4] = g_c * 0.1353352832366127f * (1.0f - th4 * th4);
+                g_q[v * 5 + 3] = g_sd * 3.0f * qb::sech2f_(qv[3]);
+                g_q[v * 5 + 4] = g_c * 0.1353352832366127f * qb::sech2f_(qv[4]);
                 if (nll_kl) nll_kl[v] = make_float2(nll, kl);
                 s_nll += nll * m;
                 s_kl += m > 0.0f ? kl : 0.0f;
@@ -406,6 +415,7 @@ __global__ __launch_bounds__(kGenBlock) void elbo_bwd_generic_kernel(
             // prepare_lik<T, SE, true>: se_norm on the data, yt = x / norm, 1 / sigma = exp(-log sigma)
             const float nt = c.multi_norm ? (xv[se - 1] + xv[se] + xv[se + 1]) / 3.0f + 1e-3f : xv[se] + 1e-3f;
             const float inv_nt = qb::rcpf_(nt);
+            const int se1 = c.multi_norm ? -1 : se;   // the tau of single-image normalisation (-1: none), see d_se
             float ls = 0.0f;
             for (int t = 0; t < T; ++t) {
                 const float l = lv[t];
@@ -445,7 +455,8 @@ __global__ __launch_bounds__(kGenBlock) void elbo_bwd_generic_kernel(
                     // se_norm on the prediction
                     float np_ = gen_signal(L, fv, se).s;
                     if (c.multi_norm) np_ = (gen_signal(L, fv, se - 1).s + np_ + gen_signal(L, fv, se + 1).s) / 3.0f;
-                    const float inv_np = qb::rcpf_(np_ + 1e-3f);
+                    const float np1 = np_ + 1e-3f, inv_np = qb::rcpf_(np1);
+                    const float d_se = (((1e-3f * (nt - np1)) * inv_nt) * inv_np);   // y - yhat at se1, as elbo_bwd_kernel
                     // per-draw factors of the slopes (fwd_signal_grad): tissue exp(-dbv F(x)), x proportional to oef;
                     // blood exp(-g B), g proportional to oef^2
                     const float ko = -dbv * inv_oef, kb = (2.0f * QB_LN2) * fv.ng * inv_oef;
@@ -461,8 +472,9 @@ __global__ __launch_bounds__(kGenBlock) void elbo_bwd_generic_kernel(
                             const float yp = sg.s * inv_np;
                             r = (yt[t * kGenBlock] - yp) * inv_s;
                         }
+                        const float rg = t == se1 ? d_se * inv_s : r;   // wave-uniform: r as d / d log sigma_t takes it
                         acc = fmaf(r, r, acc);
-                        const float dls = 1.0f - r * r;           // d/d log sigma_t of log sigma_t + r^2 / 2
+                        const float dls = 1.0f - rg * rg;         // d/d log sigma_t of log sigma_t + r^2 / 2
                         if (LPV > 1) gl[t * kGenBlock] += dls;
                         else if (g == 0 && d == 0) gv[t] = dls * wn;   // the voxel's first draw (the lane walks them in order)
                         else gv[t] = fmaf(dls, wn, gv[t]);
@@ -600,13 +612,11 @@ __global__ __launch_bounds__(kGenBlock) void elbo_bwd_generic_kernel(
             const float kl = K > 0 ? voxel_sum(kl_sum) / (float)K : 0.0f;
             if (part == 0) {
                 // transform_std / transform_offdiag (model.py:288-294), as in elbo_bwd_kernel
-                const float th1 = (qm.s_o + 1.0f) * (1.0f / 3.0f), th3 = (qm.s_d + 1.0f) * (1.0f / 3.0f);
-                const float th4 = qm.c * 7.38905609893065f;
                 g_q[v * 5 + 0] = g_mu_o;
-                g_q[v * 5 + 1] = g_so * 3.0f * (1.0f - th1 * th1);
+                g_q[v * 5 + 1] = g_so * 3.0f * qb::sech2f_(qv[1]);
                 g_q[v * 5 + 2] = g_mu_d;
-                g_q[v * 5 + 3] = g_sd * 3.0f * (1.0f - th3 * th3);
-                g_q[v * 5 + 4] = g_c * 0.1353352832366127f * (1.0f - th4 * th4);
+                g_q[v * 5 + 3] = g_sd * 3.0f * qb::sech2f_(qv[3]);
+                g_q[v * 5 + 4] = g_c * 0.1353352832366127f * qb::sech2f_(qv[4]);
                 if (nll_kl) nll_kl[v] = make_float2(nll, kl);
                 s_nll += nll * m;
                 s_kl += m > 0.0f ? kl : 0.0f;

@@ -318,14 +318,12 @@ __global__ __launch_bounds__(kBlock) void iw_bwd_kernel(
         const float inv2 = inv1 * inv1;
         if (part == 0) {
             // transform_std / transform_offdiag (model.py:288-294): s = 3 tanh(raw) - 1, c = tanh(raw) e^-2
-            const float th1 = (qm.s_o + 1.0f) * (1.0f / 3.0f), th3 = (qm.s_d + 1.0f) * (1.0f / 3.0f);
-            const float th4 = qm.c * 7.38905609893065f;
             const float wq = m * inv2;   // a voxel outside the mask writes exact zeros (its draws may be NaN)
             g_q[v * 5 + 0] = in ? wq * h[0] : 0.0f;
-            g_q[v * 5 + 1] = in ? wq * (h[1] * qm.e_so) * 3.0f * (1.0f - th1 * th1) : 0.0f;
+            g_q[v * 5 + 1] = in ? wq * (h[1] * qm.e_so) * 3.0f * qb::sech2f_(qv[1]) : 0.0f;
             g_q[v * 5 + 2] = in ? wq * h[2] : 0.0f;
-            g_q[v * 5 + 3] = in ? wq * (h[3] * qm.e_sd) * 3.0f * (1.0f - th3 * th3) : 0.0f;
-            g_q[v * 5 + 4] = in ? wq * h[4] * 0.1353352832366127f * (1.0f - th4 * th4) : 0.0f;
+            g_q[v * 5 + 3] = in ? wq * (h[3] * qm.e_sd) * 3.0f * qb::sech2f_(qv[3]) : 0.0f;
+            g_q[v * 5 + 4] = in ? wq * h[4] * 0.1353352832366127f * qb::sech2f_(qv[4]) : 0.0f;
             const float lp = Mx + (logf(s1) - logf((float)K));
             const float el = slw / (float)K;
             if (out) {

@@ -228,11 +228,9 @@ __global__ __launch_bounds__(kBlock) void refine_kernel(
             if (j == 0) loss0 = lj;
             if (j >= steps - tail) loss_tail += lj;
             // transform_std / transform_offdiag (model.py:288-294): s = 3 tanh(raw) - 1, c = tanh(raw) e^-2
-            const float th1 = (qm.s_o + 1.0f) * (1.0f / 3.0f), th3 = (qm.s_d + 1.0f) * (1.0f / 3.0f);
-            const float th4 = qm.c * 7.38905609893065f;
-            g[1] *= 3.0f * (1.0f - th1 * th1);
-            g[3] *= 3.0f * (1.0f - th3 * th3);
-            g[4] *= 0.1353352832366127f * (1.0f - th4 * th4);
+            g[1] *= 3.0f * qb::sech2f_(qv[1]);
+            g[3] *= 3.0f * qb::sech2f_(qv[3]);
+            g[4] *= 0.1353352832366127f * qb::sech2f_(qv[4]);
             const float lr = fmaf(0.5f * (ra.lr - ra.lr_final), 1.0f + cosf((float)M_PI * ((float)j / (float)steps)),
                                   ra.lr_final);
             if (ra.adam) {
@@ -433,11 +431,9 @@ __global__ __launch_bounds__(kBlock) void refine_tv_step_kernel(
             g[0] += st.w * go * so * (1.0f - so);
             g[2] += st.w * gd * sd * (1.0f - sd);
         }
-        const float th1 = (qm.s_o + 1.0f) * (1.0f / 3.0f), th3 = (qm.s_d + 1.0f) * (1.0f / 3.0f);
-        const float th4 = qm.c * 7.38905609893065f;
-        g[1] *= 3.0f * (1.0f - th1 * th1);
-        g[3] *= 3.0f * (1.0f - th3 * th3);
-        g[4] *= 0.1353352832366127f * (1.0f - th4 * th4);
+        g[1] *= 3.0f * qb::sech2f_(qv[1]);
+        g[3] *= 3.0f * qb::sech2f_(qv[3]);
+        g[4] *= 0.1353352832366127f * qb::sech2f_(qv[4]);
         const float lr = fmaf(0.5f * (ra.lr - ra.lr_final), 1.0f + cosf((float)M_PI * ((float)j / (float)steps)),
                               ra.lr_final);
         if (ra.adam) {

@@ -27,16 +27,19 @@ def logits(q, z):
     return np.stack([a, b], -1)
 
 
-def nll_parts(o, x, q, sigma, z):
+def nll_parts(o, x, q, sigma, z, jac=signal_jac_fd, scales=False):
     """Per draw: d nll / du [N, K, 2] (through forward_transform, the signal model and the normalisation) and
-    d nll / d log sigma [N, K, T] (the NLL of fine_tune_loss_fn restated as in _refine_reference.nll_grad)."""
+    d nll / d log sigma [N, K, T] (the NLL of fine_tune_loss_fn restated as in _refine_reference.nll_grad).
+    jac(o, y) -> [V, T, 2] is the signal Jacobian (default: central differences of the value).  scales: also the
+    cancellation-aware sizes of the two, the same sums with every per-tau term in absolute value and the residual
+    entering as (|yt| + |yp|) / sigma (tests/_elbo_bwd_reference.py states the measure)."""
     u = logits(q, z)
     N, K = u.shape[:2]
     T = o.T
     sa, sb = 1.0 / (1.0 + np.exp(-u[..., 0])), 1.0 / (1.0 + np.exp(-u[..., 1]))
     y = np.stack([sa * OEF_RANGE + MIN_OEF, sb * DBV_RANGE + MIN_DBV], -1).reshape(-1, 2)
     pred = np.asarray(o.signal_fwd(y), np.float64).reshape(N, K, T)
-    jac = signal_jac_fd(o, y).reshape(N, K, T, 2)
+    jac = np.asarray(jac(o, y), np.float64).reshape(N, K, T, 2)
     cfg = o.cfg
     se = cfg.se_idx
     w = np.zeros(T)
@@ -63,21 +66,31 @@ def nll_parts(o, x, q, sigma, z):
     gpred = gv / npred - (gv * pred).sum(-1, keepdims=True) / npred ** 2 * w
     ga = (gpred * jac[..., 0]).sum(-1) * OEF_RANGE * sa * (1.0 - sa)
     gb = (gpred * jac[..., 1]).sum(-1) * DBV_RANGE * sb * (1.0 - sb)
-    return np.stack([ga, gb], -1), 1.0 - dr * r
+    if not scales:
+        return np.stack([ga, gb], -1), 1.0 - dr * r
+    wr = dr / np.where(r == 0.0, 1.0, r) if cfg.use_student_t else 1.0     # d nll / dr = wr r
+    av = wr * (np.abs(yt[:, None, :]) + np.abs(yp)) / s / s * np.abs(dyp)
+    a1 = (av * np.abs(pred)).sum(-1, keepdims=True) / npred ** 2
+    au = [((av / np.abs(npred) * np.abs(jac[..., k])).sum(-1) + a1[..., 0] * (w * np.abs(jac[..., k])).sum(-1)) * f
+          for k, f in ((0, OEF_RANGE * sa * (1.0 - sa)), (1, DBV_RANGE * sb * (1.0 - sb)))]
+    return np.stack([ga, gb], -1), 1.0 - dr * r, np.stack(au, -1), 1.0 + np.abs(dr * r)
 
 
-def kl_u_grad(q, prior, z):
+def kl_u_grad(q, prior, z, scales=False):
     """d (log q(u) - log p(u)) / du [N, K, 2] per draw with q held inside log q: L_p^-T w_p - L_q^-T w_q of the
-    clipped logits (the clip passes gradient, model.py:395), as elbo_bwd_kernel's general KL loop."""
+    clipped logits (the clip passes gradient, model.py:395), as elbo_bwd_kernel's general KL loop.
+    scales: also |L_p^-T w_p| + |L_q^-T w_q|, the size of the two terms before they cancel."""
     u = np.clip(logits(q, z), -LOGIT_CLIP, LOGIT_CLIP)
-    g = 0.0
+    g = a = 0.0
     for heads, sign in ((prior, 1.0), (q, -1.0)):
         h = np.asarray(heads, np.float64)
         _, _, _, i_so, i_sd, i_bl = _chol_inv(h)
         r0, r1 = u[..., 0] - h[:, 0:1], u[..., 1] - h[:, 2:3]
         w0, w1 = r0 * i_so[:, None], r1 * i_sd[:, None] + r0 * i_bl[:, None]
-        g = g + sign * np.stack([w0 * i_so[:, None] + w1 * i_bl[:, None], w1 * i_sd[:, None]], -1)
-    return g
+        t = np.stack([w0 * i_so[:, None] + w1 * i_bl[:, None], w1 * i_sd[:, None]], -1)
+        g = g + sign * t
+        a = a + np.abs(t)
+    return (g, a) if scales else g
 
 
 def chain_u(q, z, gu):
@@ -94,21 +107,26 @@ def softmax(lw):
     return e / e.sum(1, keepdims=True)
 
 
-def iw_grad_reference(o, x, q, prior, sigma, z, mask=None):
-    """dict(g_q [N, 5] (DReG, raw heads), g_log_sigma [N, T], log_p, lw [N, K], w [N, K] normalised weights), the
-    outputs of qbold_log_evidence_bwd for explicit normals z [N, K, 2] (unnormalised by sum(mask); mask None = 1)."""
+def iw_grad_reference(o, x, q, prior, sigma, z, mask=None, jac=signal_jac_fd):
+    """dict(g_q [N, 5] (DReG, raw heads), g_log_sigma [N, T], log_p, lw [N, K], w [N, K] normalised weights, A_q, A_ls),
+    the outputs of qbold_log_evidence_bwd for explicit normals z [N, K, 2] (unnormalised by sum(mask); mask None = 1).
+    jac: the signal Jacobian, as nll_parts.  A_q [N, 5], A_ls [N, T]: the same sums with every per-draw term in absolute
+    value (nll_parts' and kl_u_grad's scales), the per-voxel measure of tests/_elbo_bwd_reference.py."""
     q = np.asarray(q, np.float64)
     N, K = np.asarray(z).shape[:2]
     m = np.ones(N) if mask is None else np.where(np.asarray(mask, np.float64) > 0, np.asarray(mask, np.float64), 0.0)
     lw, _ = log_weights(o, x, q, prior, sigma, z)
     w = softmax(lw)
-    gn_u, gn_ls = nll_parts(o, x, q, sigma, z)
-    h = gn_u + kl_u_grad(q, prior, z)               # -(d log w / du) with q held
+    gn_u, gn_ls, an_u, an_ls = nll_parts(o, x, q, sigma, z, jac=jac, scales=True)
+    gk_u, ak_u = kl_u_grad(q, prior, z, scales=True)
+    h = gn_u + gk_u                                 # -(d log w / du) with q held
     g_q = to_raw(q, chain_u(q, z, (w ** 2)[..., None] * h)) * m[:, None]
     g_ls = (w[..., None] * gn_ls).sum(1) * m[:, None]
+    A_q = np.abs(to_raw(q, chain_u(q, np.abs(z), (w ** 2)[..., None] * (an_u + ak_u)))) * m[:, None]
+    A_ls = (w[..., None] * an_ls).sum(1) * m[:, None]
     M = lw.max(1)
     log_p = M + np.log(np.exp(lw - M[:, None]).sum(1)) - np.log(K)
-    return dict(g_q=g_q, g_log_sigma=g_ls, log_p=log_p, lw=lw, w=w)
+    return dict(g_q=g_q, g_log_sigma=g_ls, log_p=log_p, lw=lw, w=w, A_q=A_q, A_ls=A_ls)
 
 
 def frozen_log_weights(o, x, q, q_frozen, prior, sigma, z):

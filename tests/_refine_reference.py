@@ -32,9 +32,11 @@ def signal_jac_fd(o, y, h=1e-6):
     return np.stack(cols, -1)
 
 
-def nll_grad(o, x, q, sigma, z):
+def nll_grad(o, x, q, sigma, z, jac=None, scales=False):
     """Mean over the S draws of d nll(x | reparam(q, z_s)) / d(mu_o, s_o, mu_d, s_d, c) [N, 5] (logit-space parameters,
-    before the raw chain); z [N, S, 2]."""
+    before the raw chain); z [N, S, 2].  jac(o, y) -> [V, T, 2]: the signal Jacobian (None: signal_jac_fd).  scales:
+    also the same mean with every per-tau, per-draw term in absolute value and the residual entering as
+    (|yt| + |yp|) / sigma (the per-voxel measure of tests/_elbo_bwd_reference.py)."""
     q = np.asarray(q, np.float64)
     z = np.asarray(z, np.float64)
     N, S = z.shape[:2]
@@ -46,7 +48,7 @@ def nll_grad(o, x, q, sigma, z):
     sa, sb = 1.0 / (1.0 + np.exp(-a)), 1.0 / (1.0 + np.exp(-b))
     y = np.stack([sa * OEF_RANGE + MIN_OEF, sb * DBV_RANGE + MIN_DBV], -1).reshape(-1, 2)
     pred = np.asarray(o.signal_fwd(y), np.float64).reshape(N, S, T)
-    jac = signal_jac_fd(o, y).reshape(N, S, T, 2)
+    jac = np.asarray((jac or signal_jac_fd)(o, y), np.float64).reshape(N, S, T, 2)
     cfg = o.cfg
     se = cfg.se_idx
     w = np.zeros(T)
@@ -76,7 +78,16 @@ def nll_grad(o, x, q, sigma, z):
     ga = g_oef * OEF_RANGE * sa * (1.0 - sa)
     gb = g_dbv * DBV_RANGE * sb * (1.0 - sb)
     g = np.stack([ga, ga * z0 * np.exp(so)[:, None], gb, gb * z1 * np.exp(sd)[:, None], gb * z0], -1)
-    return g.mean(1)
+    if not scales:
+        return g.mean(1)
+    wr = dr / np.where(r == 0.0, 1.0, r) if cfg.use_student_t else 1.0     # d nll / dr = wr r
+    av = wr * (np.abs(yt[:, None, :]) + np.abs(yp)) / s / s * np.abs(dyp)
+    a1 = (av * np.abs(pred)).sum(-1, keepdims=True) / npred ** 2
+    aa, ab = [((av / np.abs(npred) * np.abs(jac[..., k])).sum(-1) + a1[..., 0] * (w * np.abs(jac[..., k])).sum(-1)) * f
+              for k, f in ((0, OEF_RANGE * sa * (1.0 - sa)), (1, DBV_RANGE * sb * (1.0 - sb)))]
+    a0, a1z = np.abs(z0), np.abs(z1)
+    A = np.stack([aa, aa * a0 * np.exp(so)[:, None], ab, ab * a1z * np.exp(sd)[:, None], ab * a0], -1)
+    return g.mean(1), A.mean(1)
 
 
 def kl_closed_and_grad(q, prior):
@@ -110,10 +121,15 @@ def to_raw(q, g):
     return out
 
 
-def step_grad(o, x, q, prior, sigma, z):
-    """d/d raw heads of mean_s nll(x | reparam(q, z_s)) + KL(q || prior) [N, 5]: one refinement step's gradient."""
+def step_grad(o, x, q, prior, sigma, z, jac=None, scales=False):
+    """d/d raw heads of mean_s nll(x | reparam(q, z_s)) + KL(q || prior) [N, 5]: one refinement step's gradient.
+    jac: the signal Jacobian, as nll_grad.  scales: also A [N, 5], nll_grad's absolute sums plus |d KL| through the
+    same chain."""
     _, gk = kl_closed_and_grad(q, prior)
-    return to_raw(q, nll_grad(o, x, q, sigma, z) + gk)
+    if not scales:
+        return to_raw(q, nll_grad(o, x, q, sigma, z, jac=jac) + gk)
+    gn, an = nll_grad(o, x, q, sigma, z, jac=jac, scales=True)
+    return to_raw(q, gn + gk), np.abs(to_raw(q, an + np.abs(gk)))
 
 
 def cosine_lr(j, steps, lr, lr_final):

@@ -103,6 +103,42 @@ def test_one_sgd_step_is_the_gradient(params, case):
         o64.lib.qbo_set_node0_zero(0)
 
 
+@pytest.mark.parametrize("S", [1, 5])
+def test_one_sgd_step_under_the_default_node0_policy(params, S):
+    """The shipped gradient policy (a context whose grad_node0 nobody set: refine_kernels.hip's restatement of
+    fwd_signal_grad with node 0's slope) at T = 11: one SGD step at lr = 1, so that q_in - q_out is the gradient to
+    float32 rounding, against step_grad given the oracle's analytic Jacobian.  Every head of every voxel, |d| <= 2e-4 A
+    with A the same sum in absolute values (tests/_elbo_bwd_reference.py), next to test_one_sgd_step_is_the_gradient's
+    column-max bound; the reference of the other policy is missed by more than 10 x."""
+    from _elbo_bwd_reference import analytic_jac
+    from oracle.oracle import Oracle
+    from qbold_vi_amd.ops import Context
+    c = Context(params, True, True)
+    o32 = Oracle("f32", params)
+    o64 = Oracle("f64", params, node0_zero=True)
+    try:
+        n = 48
+        x, q, prior, sigma = _case(o32, params, n, 5)
+        z = np.zeros((n, 1, padded_draws(S), 2), np.float32)
+        z[:, 0, :S] = np.random.default_rng(8).standard_normal((n, S, 2))
+        q64 = q.astype(np.float64)
+        zs = z[:, 0, :S].astype(np.float64)
+        q_out = c.refine_posterior(dev(x), None, dev(q), dev(prior), dev(sigma), steps=1, S=S, lr=1.0, lr_final=1.0,
+                                   optimizer="sgd", z=dev(z))
+        g = q64 - q_out.cpu().numpy().astype(np.float64)
+        ref, A = step_grad(o64, x, q64, prior, sigma, zs, jac=analytic_jac, scales=True)
+        other = step_grad(o64, x, q64, prior, sigma, zs)
+        A = A + 2.0 ** -23 * (np.abs(q64) + np.abs(g))   # the float32 rounding of q_in - q_out itself
+        worst, apart = float(np.max(np.abs(g - ref) / A)), float(np.max(np.abs(g - other) / A))
+        print(f"S={S}: worst |d| / A {worst:.2e}; against the other policy {apart:.2e}")
+        for k in range(5):
+            assert np.max(np.abs(g[:, k] - ref[:, k])) / (np.abs(ref[:, k]).max() + 1e-3) < 2e-3, k
+        assert worst <= 2e-4
+        assert apart > 2e-3
+    finally:
+        o64.lib.qbo_set_node0_zero(0)
+
+
 @pytest.fixture(scope="module")
 def data4k(params):
     from oracle.oracle import Oracle
