@@ -586,6 +586,49 @@ int qbold_posterior_predictive(const qbold_ctx* ctx, const float* x, const float
                                const float* sigma, const float* z, int L, uint64_t seed, int64_t voxel0,
                                float* out, float* curves, double* sums, void* workspace, int64_t N, void* stream);
 
+/* Pareto-smoothed importance-sampling leave-one-out cross-validation per voxel and per tau image (this package's
+ * addition; Vehtari, Gelman & Gabry 2017; with draws from a variational posterior Yao et al. 2018, Magnusson et al.
+ * 2019).  For a voxel with heads q, prior, exponentiated sigma and K draws theta_k ~ q -- the draws of
+ * qbold_log_evidence_draws: explicit z [N][K][2], or the Philox stream 6 keyed (seed, voxel0 + i), draw k here is draw
+ * k there --
+ *   log w_k   = qbold_log_evidence_draws' value, -nll - (log q - log p) on the draw
+ *   ll_{t,k}  = log p(y_t | theta_k), qbold_posterior_predictive's per-tau term (Gaussian or Student-t, in the
+ *               likelihood's own normalised or logged space); sum_t ll_{t,k} = -nll_k
+ *   row t < T : rho_{t,k} = log w_k - ll_{t,k}, the log-ratio of the posterior without image t;  row T: log w_k.
+ * Every row goes through qbold_psis as that entry defines it (tail rule, ties, the k^ = +inf cases, NaN rows): row t
+ * gives the normalised smoothed weights w~^(t), row T gives w~.  With m_t = max_k ll_{t,k}
+ *   elpd_t = m_t + log sum_k w~^(t)_k exp(ll_{t,k} - m_t),     lppd_t = m_t + log sum_k w~_k exp(ll_{t,k} - m_t)
+ *   out [N][QBOLD_LOO_OUT]:
+ *     0 elpd_loo  = sum_t elpd_t
+ *     1 p_loo     = lppd - elpd_loo
+ *     2 lppd      = sum_t lppd_t
+ *     3 khat_max  = max_t k^_t (+inf beats every finite value; a NaN k^, from a NaN row, beats all)
+ *     4 the lowest tau index attaining it, as a float
+ *     5 khat_full = row T's k^
+ *   pointwise [N][T][3] or NULL: (elpd_t, k^_t, lppd_t)
+ *   log_ratio [N][T + 1][K] or NULL: the rows above;  loglik [N][T][K] or NULL: ll.  When given, they are where the rows
+ *     are written: the caller sees exactly what the PSIS stage read.
+ *   Voxels with mask <= 0 (or NaN) are not read; their outputs and rows are NaN and they add nothing to the sums; mask
+ *     NULL = ones.
+ *   sums: DEVICE double[4] = (sum m elpd_loo, sum m p_loo, sum m [khat_max > 0.7], sum m) over the voxels with m > 0,
+ *     overwritten; accumulated in doubles in a fixed order, no atomics.
+ *   workspace: qbold_loo_workspace_bytes(ctx, K, N) bytes, 16-byte aligned, caller-owned: per voxel
+ *     4 K (3 T + 2) + 16 (T + 1) bytes (loglik, log_ratio, the smoothed weights of the T + 1 rows, qbold_psis' out), each
+ *     of the four sections rounded up to 256 bytes, plus 32 bytes per block of the reduction (8 blocks per compute
+ *     unit).  The size does not depend on whether log_ratio / loglik are given.
+ * A high k^_t says that image t alone dominates the voxel's fit -- the signature of a corrupted tau image; elpd_loo
+ * compares forward-model variants.  A voxel's outputs are the same bits at any batch position, under any sharding by
+ * voxel0 and from run to run.  Configurations qbold_log_evidence_draws accepts (table mode; T = 11 / 24 with every
+ * likelihood switch; every other T <= 64 with the Gaussian likelihood on linear data); QBOLD_ERR_UNSUPPORTED otherwise.
+ * QBOLD_ERR_INVALID for K outside [QBOLD_PSIS_MIN_K, QBOLD_PSIS_MAX_K], N < 0, a NULL out / sums / workspace, or a NULL
+ * input buffer when N > 0; N = 0 succeeds with zero sums.  qbold_loo_workspace_bytes returns QBOLD_ERR_INVALID for a
+ * NULL context, K outside that range or N < 0.  x, q, prior, sigma, stream as qbold_log_evidence_fwd. */
+#define QBOLD_LOO_OUT 6
+int64_t qbold_loo_workspace_bytes(const qbold_ctx* ctx, int K, int64_t N);
+int qbold_loo(const qbold_ctx* ctx, const float* x, const float* mask, const float* q, const float* prior,
+              const float* sigma, const float* z, int K, uint64_t seed, int64_t voxel0, float* out, float* pointwise,
+              float* log_ratio, float* loglik, double* sums, void* workspace, int64_t N, void* stream);
+
 /* ---- gradients (training) ------------------------------------------------------------------- */
 /* Adjoint of qbold_elbo_fwd with respect to the encoder's head outputs: what TensorFlow autodiff
  * yields through build_fine_tuner's sampling + fine_tune_loss_fn + kl_loss (model.py:239-286,

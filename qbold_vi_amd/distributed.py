@@ -126,3 +126,10 @@ def ppc_from_sums(sums):
     qbold_posterior_predictive (double[4]: sum m elpd_waic, sum m p_waic, sum m ppp, sum m); they add across shards
     (allreduce_)."""
     return sums[0] / sums[3], sums[1] / sums[3], sums[2] / sums[3]
+
+
+def loo_from_sums(sums):
+    """(mean elpd_loo, mean p_loo, fraction of voxels with khat_max > 0.7) over the masked voxels from the reduced sums
+    of qbold_loo (double[4]: sum m elpd_loo, sum m p_loo, sum m [khat_max > 0.7], sum m); they add across shards
+    (allreduce_)."""
+    return sums[0] / sums[3], sums[1] / sums[3], sums[2] / sums[3]

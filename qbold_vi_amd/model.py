@@ -421,6 +421,39 @@ class FineTuner:
         return res
 
 
+    def loo(self, data, mask, prior, q=None, no_samples=256, seed=1, voxel0=0, want_pointwise=False):
+        """PSIS leave-one-out cross-validation per voxel and per tau image (Context.loo; Vehtari, Gelman & Gabry 2017)
+        of `no_samples` = K draws (25 <= K <= 1024, the draws of log_evidence() for the same seed) for the heads q
+        [..., 5] (None: the encoder heads of encoder_model.predict; refine()'s output, say) and the sigma that goes with
+        them.  Shaped like the data's spatial dims:
+          elpd_loo   sum_t log p(y_t | y_-t): compares forward-model variants on the same data
+          p_loo      lppd - elpd_loo, the effective number of parameters;  lppd from the smoothed full-data weights
+          khat_max   the largest Pareto k^ over the tau images (above 0.7: elpd_loo is not reliable there, and ONE image
+                     dominates the voxel's fit -- the signature of a corrupted tau image), worst_tau its index
+          khat_full  the k^ of the full-data weights (log_evidence(psis=True)'s khat)
+          elpd_t, khat_t, lppd_t [..., T] (want_pointwise)
+        and the masked sums with mean_elpd_loo, mean_p_loo, frac_khat_bad (distributed.loo_from_sums).  Voxels outside
+        the mask are NaN."""
+        from .distributed import loo_from_sums
+        tr = self._trainer
+        self._check_mvn_family("loo")
+        T = data.shape[-1]
+        x = _flat(data, T)
+        m = None if mask is None else mask.reshape(-1)
+        p5 = _flat(prior, prior.shape[-1]).contiguous()
+        q, sg = self._heads_and_sigma(data, q)
+        r = tr._ctx.loo(x, m, q, p5, sg, int(no_samples), seed=seed, voxel0=voxel0, want_pointwise=want_pointwise)
+        lead = data.shape[:-1]
+        res = {k: r["out"][:, i].reshape(lead) for i, k in enumerate(tr._ctx.LOO_COLUMNS)}
+        if want_pointwise:
+            pw = r["pointwise"]
+            res.update(elpd_t=pw[..., 0].reshape(lead + (T,)), khat_t=pw[..., 1].reshape(lead + (T,)),
+                       lppd_t=pw[..., 2].reshape(lead + (T,)))
+        el, pl, bad = loo_from_sums(r["sums"])
+        res.update(sums=r["sums"], mean_elpd_loo=el, mean_p_loo=pl, frac_khat_bad=bad)
+        return res
+
+
 class EncoderTrainer:
     def __init__(self,
                  system_params,
@@ -768,7 +801,8 @@ class EncoderTrainer:
 
     def save_predictions(self, model, data, filename, transform_directory=None, use_first_op=True,
                          fine_tuner_model=None, priors=None, iw_samples=None, refine_steps=None,
-                         posterior_grid=None, ppc_samples=None, refine_smoothness_weight=0.0, psis=False):
+                         posterior_grid=None, ppc_samples=None, refine_smoothness_weight=0.0, psis=False,
+                         loo_samples=None):
         """model.py:772-887: write `<filename>_{oef,dbv,r2p,logstds}.nii.gz` (posterior means of
         OEF / DBV / R2' over 200 draws and their variances) and, with a fine tuner,
         `_likelihood` (per-voxel NLL averaged over 100 stochastic passes), `_kl` (100-draw KL to
@@ -796,6 +830,10 @@ class EncoderTrainer:
         `_elpdwaic`, `_pwaic`, `_maxresid` (largest |standardised residual|) and the per-tau `_predmean`, `_predsd`,
         `_stdresid` [X, Y, Z, subj*T] (fitted curve, predictive sd, standardised residual in the likelihood's
         normalised space), zero outside the mask; these maps join the returned dict.  `_residual` is unchanged.
+        loo_samples = K (with a fine tuner, 25 <= K <= 1024; this package's addition): PSIS leave-one-out
+        cross-validation of K draws from the encoder's heads (FineTuner.loo) as `_elpdloo`, `_ploo`, `_khatloo` (the
+        largest Pareto k^ over the tau images) and `_worsttau` (its tau index), NaN outside the mask; these maps join the
+        returned dict.  None writes nothing new.
         data [subj, X, Y, Z, T+1] with the mask last; each map is stored as [X, Y, Z, subj*C].
         `transform_directory/example.nii.gz`, when present, donates its header (:794-797); the
         FSL `applywarp`/`fslmerge` MNI step (:850-879) is preprocessing outside this package and
@@ -916,6 +954,15 @@ class EncoderTrainer:
             for k, v in ppc_maps.items():
                 save_im_data(v, filename + '_' + k)
             iw_maps = dict(iw_maps or {}, **ppc_maps)
+
+        if fine_tuner_model and loo_samples:
+            lo = fine_tuner_model.loo(data[..., :-1], mask, torch.as_tensor(priors, device=data.device)[..., :self._nq],
+                                      no_samples=int(loo_samples), seed=self._seed + 59)
+            loo_maps = {k: lo[c][..., None] for k, c in (("elpdloo", "elpd_loo"), ("ploo", "p_loo"),
+                                                         ("khatloo", "khat_max"), ("worsttau", "worst_tau"))}
+            for k, v in loo_maps.items():
+                save_im_data(v, filename + '_' + k)
+            iw_maps = dict(iw_maps or {}, **loo_maps)
 
         save_im_data(means[..., 0:1], filename + '_oef')
         save_im_data(means[..., 1:2], filename + '_dbv')

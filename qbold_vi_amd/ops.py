@@ -715,6 +715,63 @@ class Context:
                    "qbold_posterior_predictive")
         return sums, out, curves
 
+    LOO_COLUMNS = ("elpd_loo", "p_loo", "lppd", "khat_max", "worst_tau", "khat_full")
+
+    def loo(self, x, mask, q, prior, sigma, K, z=None, seed=1, voxel0=0, want_pointwise=False, want_rows=False,
+            max_workspace_bytes=1 << 30):
+        """PSIS leave-one-out cross-validation per voxel and per tau image (qbold_loo; Vehtari, Gelman & Gabry 2017) on
+        the K draws of log_evidence_draws (25 <= K <= 1024; Philox stream 6 unless z [N, K, 2] is given).  Returns a dict:
+          sums       double[4] device tensor = (sum [m>0] m elpd_loo, sum [m>0] m p_loo, sum [m>0] m [khat_max > 0.7],
+                     sum [m>0] m)
+          out        [N, 6] with the columns of LOO_COLUMNS
+          pointwise  [N, T, 3] = (elpd_t, k^_t, lppd_t) (want_pointwise) or None
+          log_ratio  [N, T + 1, K], loglik [N, T, K]: the rows the PSIS stage read (want_rows) or None
+        Voxels with mask <= 0 come back NaN.  The volume runs in voxel chunks whose workspace
+        (qbold_loo_workspace_bytes) stays under max_workspace_bytes (one voxel at the least); chunks pass their own
+        voxel0, so the per-voxel results do not depend on the chunking, and the chunk sums are added in float64."""
+        K = int(K)
+        if not _lib.QBOLD_PSIS_MIN_K <= K <= _lib.QBOLD_PSIS_MAX_K:
+            raise ValueError("loo: need 25 <= K <= 1024")
+        x = _f32(x, "x", self.T)
+        T = self.T
+        N = x.numel() // T
+        x = x.reshape(N, T)
+        rows = lambda t, *s: t.reshape((t.numel() // math.prod(s),) + s)   # noqa: E731  (an empty batch has no -1)
+        q, prior, sigma = rows(_f32(q, "q", 5), 5), rows(_f32(prior, "prior", 5), 5), rows(_f32(sigma, "sigma", T), T)
+        mask = _f32(mask, "mask").reshape(mask.numel()) if mask is not None else None
+        z = rows(_f32(z, "z", 2), K, 2) if z is not None else None
+        if z is not None and z.shape[0] != N:
+            raise ValueError("z must be [N, K, 2]")
+        if q.shape[0] != N or prior.shape[0] != N or sigma.shape[0] != N or (mask is not None and mask.numel() != N):
+            raise ValueError("loo: q [N, 5], prior [N, 5], sigma [N, T] and mask [N] must match x [N, T]")
+        ws_bytes = lambda n: int(self.lib.qbold_loo_workspace_bytes(self.handle, K, int(n)))   # noqa: E731
+        per_voxel = 4 * K * (3 * T + 2) + 16 * (T + 1)
+        chunk = max(min((int(max_workspace_bytes) - ws_bytes(0)) // per_voxel, N), 1)
+        while chunk > 1 and ws_bytes(chunk) > int(max_workspace_bytes):   # the sections' rounding
+            chunk -= 1
+        dev = x.device
+        ws = torch.empty(ws_bytes(min(chunk, N)), dtype=torch.uint8, device=dev)
+        out = torch.empty((N, _lib.QBOLD_LOO_OUT), dtype=torch.float32, device=dev)
+        pw = torch.empty((N, T, 3), dtype=torch.float32, device=dev) if want_pointwise else None
+        lr = torch.empty((N, T + 1, K), dtype=torch.float32, device=dev) if want_rows else None
+        ll = torch.empty((N, T, K), dtype=torch.float32, device=dev) if want_rows else None
+        total = torch.zeros(4, dtype=torch.float64, device=dev)
+        part = torch.empty(4, dtype=torch.float64, device=dev)
+        sl = lambda t, a, b: None if t is None else t[a:b]   # noqa: E731
+        if N == 0:   # the entry still runs (it zeroes the sums); an empty tensor has no address to give it
+            spare = torch.empty((1, _lib.QBOLD_LOO_OUT), dtype=torch.float32, device=dev)
+            _lib.check(self.lib.qbold_loo(self.handle, None, None, None, None, None, None, K, int(seed), int(voxel0),
+                                          _ptr(spare), None, None, None, _ptr(total), _ptr(ws), 0, _stream()),
+                       "qbold_loo")
+        for a in range(0, N, chunk):
+            b = min(a + chunk, N)
+            _lib.check(self.lib.qbold_loo(self.handle, _ptr(x[a:b]), _ptr(sl(mask, a, b)), _ptr(q[a:b]),
+                                          _ptr(prior[a:b]), _ptr(sigma[a:b]), _ptr(sl(z, a, b)), K, int(seed),
+                                          int(voxel0) + a, _ptr(out[a:b]), _ptr(sl(pw, a, b)), _ptr(sl(lr, a, b)),
+                                          _ptr(sl(ll, a, b)), _ptr(part), _ptr(ws), b - a, _stream()), "qbold_loo")
+            total = total + part
+        return dict(sums=total, out=out, pointwise=pw, log_ratio=lr, loglik=ll)
+
     def vi_fwd_exact(self, weights, x, mask, prior, S=1, K=70, seed=1, voxel0=0):
         """The same evaluation with the encoder on the exact-float32 layer-wise path (f32-input MFMA GEMMs,
         qbold_encoder_train_fwd) -- no f16 operand split, so no 65504 operand limit.  Slow (one launch per layer,

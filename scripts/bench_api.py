@@ -185,6 +185,9 @@ def main():
         "posterior_predictive(L=256)": (lambda: ctx.posterior_predictive(x, mask, q, sg, 256), 8 * T + 24 + 24),
         "posterior_predictive(L=256,curves)": (lambda: ctx.posterior_predictive(x, mask, q, sg, 256, want_curves=True),
                                                8 * T + 24 + 24 + 12 * T),
+        # PSIS leave-one-out: inputs and out, plus the rows through the three stages (rows kernel: 4 K (2 T + 1) out and
+        # 4 K T read back; qbold_psis: 4 K (T + 1) in and out; closing kernel: 4 K (2 T + 1) in); 1 GiB workspace chunks
+        "loo(K=100)": (lambda: ctx.loo(x, mask, q, o1, sg, 100, seed=1), 8 * T + 68 + 4 * 100 * (7 * T + 4)),
         "vi_fwd(S=32,K=70)": (lambda: ctx.vi_fwd(ew, x, mask, o1, 32, 70, seed=1), 4 * T + 52),
         "synth_loss_bwd": (lambda: st.synth_loss_bwd(y3, o1), 12 + 20 + 24),
         "wls_fit": (lambda: ctx.wls_fit(x), 4 * T + 12),
