@@ -785,9 +785,12 @@ __global__ void r2p_loss_bwd_kernel(QbDev c, const float* __restrict__ y_true, i
                 }
                 for (int d = 0; d < (two ? 2 : 1); ++d) {
                     const float z0 = zz[2 * d], z1 = zz[2 * d + 1];
-                    float a, b, oef, dbv;
+                    float a, b;
                     qb::reparam_logits(m, z0, z1, a, b);
-                    qb::forward_transform(a, b, oef, dbv);
+                    // forward_transform with the sigmoids' own e^-logit kept for their slopes
+                    const float ea = qb::exp2f_(-QB_LOG2E * a), eb = qb::exp2f_(-QB_LOG2E * b);
+                    const float sa = qb::rcpf_(1.0f + ea), sb = qb::rcpf_(1.0f + eb);
+                    const float oef = sa * QB_OEF_RANGE + QB_MIN_OEF, dbv = sb * QB_DBV_RANGE + QB_MIN_DBV;
                     const float r = (c.dw_coef * oef) * dbv;  // calculate_r2p, model.py:524-525
                     if (pass == 0) {
                         acc += r;
@@ -795,10 +798,14 @@ __global__ void r2p_loss_bwd_kernel(QbDev c, const float* __restrict__ y_true, i
                         acc += (r - mean) * (r - mean);
                     } else {
                         const float gr = A + B * (r - mean);
-                        // d sigmoid-range / d logit = (x - min) (1 - (x - min) / range)
-                        const float uo = oef - QB_MIN_OEF, ud = dbv - QB_MIN_DBV;
-                        const float da = gr * c.dw_coef * dbv * uo * (1.0f - uo * (1.0f / QB_OEF_RANGE));
-                        const float db = gr * c.dw_coef * oef * ud * (1.0f - ud * (1.0f / QB_DBV_RANGE));
+                        // d sigmoid-range / d logit = range s (1 - s) with 1 - s = s e^-logit.  Not (x - min)
+                        // (1 - (x - min) / range): at the upper end of the range that difference keeps only the
+                        // rounding of x (3e-4 relative 1e-4 below the end; MEASUREMENTS.md section 25).  e is capped
+                        // so that e = inf, s = 0 gives 0.
+                        const float so_ = QB_OEF_RANGE * sa * (sa * fminf(ea, 1e30f));
+                        const float sd_ = QB_DBV_RANGE * sb * (sb * fminf(eb, 1e30f));
+                        const float da = gr * c.dw_coef * dbv * so_;
+                        const float db = gr * c.dw_coef * oef * sd_;
                         G[0] += da;
                         G[1] += da * z0 * m.e_so;
                         G[2] += db;
@@ -819,14 +826,12 @@ __global__ void r2p_loss_bwd_kernel(QbDev c, const float* __restrict__ y_true, i
             }
         }
         if (g_q) {
-            const float th1 = (m.s_o + 1.0f) * (1.0f / 3.0f), th3 = (m.s_d + 1.0f) * (1.0f / 3.0f);
-            const float th4 = m.c * 7.38905609893065f;
             float* g = g_q + i * 5;
             g[0] += scale * G[0];
-            g[1] += scale * G[1] * 3.0f * (1.0f - th1 * th1);                    // transform_std
+            g[1] += scale * G[1] * 3.0f * qb::sech2f_(p[1]);                     // transform_std
             g[2] += scale * G[2];
-            g[3] += scale * G[3] * 3.0f * (1.0f - th3 * th3);
-            g[4] += scale * G[4] * 0.1353352832366127f * (1.0f - th4 * th4);      // transform_offdiag
+            g[3] += scale * G[3] * 3.0f * qb::sech2f_(p[3]);
+            g[4] += scale * G[4] * 0.1353352832366127f * qb::sech2f_(p[4]);      // transform_offdiag
         }
     }
 }
@@ -1026,11 +1031,10 @@ __global__ __launch_bounds__(256) void kl_diag_kernel(const float* __restrict__ 
         if (m > 0.0f) s_kl += kl;   // model.py:718
         s_m += m;
         if (g_q && m > 0.0f) {
-            const float to = (sqo + 1.0f) * (1.0f / 3.0f), td = (sqd + 1.0f) * (1.0f / 3.0f);  // tanh(raw)
             g_q[v * 5 + 0] += ro * ipo;
-            g_q[v * 5 + 1] += eo * 3.0f * (1.0f - to * to);   // d/ds_q = exp(2 (s_q - s_p)) - 1
+            g_q[v * 5 + 1] += eo * 3.0f * qb::sech2f_(qv[1]);   // d/ds_q = exp(2 (s_q - s_p)) - 1
             g_q[v * 5 + 2] += rd * ipd;
-            g_q[v * 5 + 3] += ed * 3.0f * (1.0f - td * td);
+            g_q[v * 5 + 3] += ed * 3.0f * qb::sech2f_(qv[3]);
         }
     }
     qb::block_partials(red, 0.0f, s_kl, s_m, partials);

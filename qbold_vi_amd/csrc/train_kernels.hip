@@ -2579,11 +2579,13 @@ __global__ void nlogp_bwd_kernel(const float* __restrict__ y_true, int ldy, cons
         const float r0 = o.l0 - m.mu_o, r1 = o.l1 - m.mu_d;
         const float w0 = r0 * m.i_so, w1 = r1 * m.i_sd + r0 * m.i_bl;
         float lv = 1.8378770664093453f + (m.s_o + m.s_d) + 0.5f * (w0 * w0 + w1 * w1) + o.jac;
-        const float th1 = (m.s_o + 1.0f) * (1.0f / 3.0f), th3 = (m.s_d + 1.0f) * (1.0f / 3.0f);
-        const float th4 = m.c * 7.38905609893065f;
-        float g1 = (1.0f - w0 * w0 - w1 * r0 * m.i_bl) * 3.0f * (1.0f - th1 * th1);
-        float g3 = (1.0f - w1 * w1) * 3.0f * (1.0f - th3 * th3);
-        float g4 = (w1 * -r0 * m.i_so * m.i_sd) * 0.1353352832366127f * (1.0f - th4 * th4);
+        // d head / d raw from the raw heads (qb::sech2f_ shares make_mvn's exp): 1 - th^2 of the rounded tanh keeps
+        // only tanh's rounding as a head saturates (MEASUREMENTS.md section 25, which also says why the slope is
+        // multiplied in before the transform's constant)
+        const float c1 = qb::sech2f_(p[1]), c3 = qb::sech2f_(p[3]), c4 = qb::sech2f_(p[4]);
+        float g1 = ((1.0f - w0 * w0 - w1 * r0 * m.i_bl) * c1) * 3.0f;
+        float g3 = ((1.0f - w1 * w1) * c3) * 3.0f;
+        float g4 = ((w1 * -r0 * m.i_so * m.i_sd) * c4) * 0.1353352832366127f;
         if (ig_a > 0.0f) {
             const float xo = 1.0f / (m.i_so * m.i_so);               // exp(s_o)^2
             const float ed = 1.0f / (m.i_sd * m.i_sd);               // exp(s_d)^2
@@ -2592,8 +2594,8 @@ __global__ void nlogp_bwd_kernel(const float* __restrict__ y_true, int ldy, cons
             lv += 2.0f * ig_c0 + (ig_a + 1.0f) * (logf(xo) + logf(xd)) + ig_b / xo + ig_b / xd;
             const float do_ = (ig_a + 1.0f) / xo - ig_b / (xo * xo);  // d / d x_o
             const float dd = (ig_a + 1.0f) / xd - ig_b / (xd * xd);   // d / d x_d
-            g1 += do_ * 2.0f * xo * 3.0f * (1.0f - th1 * th1);
-            g3 += dd * 2.0f * ed * 3.0f * (1.0f - th3 * th3);
+            g1 += do_ * 2.0f * xo * 3.0f * c1;
+            g3 += dd * 2.0f * ed * 3.0f * c3;
             g4 += dd * 2.0f * p[4];
         }
         if (loss) loss[v] = lv;
@@ -2620,14 +2622,14 @@ __global__ __launch_bounds__(256) void hyper_prior_kernel(const float* __restric
     double s_lo = 0.0, s_io = 0.0, s_ld = 0.0, s_id = 0.0;
     for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < N;
          v += (int64_t)gridDim.x * blockDim.x) {
-        const float so = qb::transform_std(q[v * 5 + 1]), sd = qb::transform_std(q[v * 5 + 3]);
+        const float ro = q[v * 5 + 1], rd = q[v * 5 + 3];
+        const float so = qb::transform_std(ro), sd = qb::transform_std(rd);
         const float lvo = 2.0f * so, lvd = 2.0f * sd;              // log v
         const float ivo = __expf(-lvo), ivd = __expf(-lvd);        // 1 / v
         if (loss) loss[v] += (c_o + (a_o + 1.0f) * lvo + b_o * ivo) + (c_d + (a_d + 1.0f) * lvd + b_d * ivd);
         if (g_q) {
-            const float to = (so + 1.0f) * (1.0f / 3.0f), td = (sd + 1.0f) * (1.0f / 3.0f);   // tanh(raw)
-            g_q[v * 5 + 1] += scale * (2.0f * (a_o + 1.0f) - 2.0f * b_o * ivo) * 3.0f * (1.0f - to * to);
-            g_q[v * 5 + 3] += scale * (2.0f * (a_d + 1.0f) - 2.0f * b_d * ivd) * 3.0f * (1.0f - td * td);
+            g_q[v * 5 + 1] += scale * (2.0f * (a_o + 1.0f) - 2.0f * b_o * ivo) * 3.0f * qb::sech2f_(ro);
+            g_q[v * 5 + 3] += scale * (2.0f * (a_d + 1.0f) - 2.0f * b_d * ivd) * 3.0f * qb::sech2f_(rd);
         }
         s_lo += lvo; s_io += ivo; s_ld += lvd; s_id += ivd;
     }
