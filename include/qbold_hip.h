@@ -629,6 +629,44 @@ int qbold_loo(const qbold_ctx* ctx, const float* x, const float* mask, const flo
               const float* sigma, const float* z, int K, uint64_t seed, int64_t voxel0, float* out, float* pointwise,
               float* log_ratio, float* loglik, double* sums, void* workspace, int64_t N, void* stream);
 
+/* Posterior calibration against a KNOWN truth (this package's addition; simulation-based calibration, Talts et al. 2018;
+ * Sailynoja et al. 2022): where the true (OEF, DBV) of a simulated voxel falls in the posterior q the encoder returned
+ * for it.  Over many voxels every column below is Uniform(0, 1) exactly when the intervals of q cover as often as they
+ * claim.  Nothing of the forward model enters: no table, no tau grid, so the entry runs on every context.
+ *   theta_true [N][2]: the known (OEF, DBV).
+ *   q [N][5]: raw heads of the use_mvg family, (mu_o, s_o, mu_d, s_d, c) = the transforms of model.py:288-294.
+ *   mask [N] or NULL (= ones): voxels with mask <= 0 (or NaN) are not read; their six outputs are NaN.
+ *   z: explicit normals [N][L][2] (exactly 2 L floats per voxel are read), or NULL for the Philox stream 6 keyed
+ *     (seed, voxel0 + i): draw k is draw k of qbold_normals(seed, 6, voxel0, L), which is draw k of
+ *     qbold_log_evidence_draws -- so a row of weights of that entry's draws lines up with the draws here.
+ *   log_w [N][L] or NULL: log-weights of the same draws, normalised or not -- qbold_psis' `weights`, or the raw log_w of
+ *     qbold_log_evidence_draws.  -inf is a zero weight; a NaN or +inf anywhere in a row, or no finite entry, makes
+ *     columns 3 - 5 of that voxel NaN and leaves columns 0 - 2 as they are.
+ * Per voxel: (a*, b*) = the truth's logits, logit(clamp((OEF - 0.04) / 0.8, 1e-6, 1 - 1e-6)) and the same with
+ * (DBV - 0.001) / 0.2 (model.py:393-398; 1 - x is formed as (0.84 - OEF) / 0.8, which does not cancel at the upper
+ * clamp);  draw k: a_k = mu_o + z0 e^{s_o}, b_k = mu_d + z0 c + z1 e^{s_d} (model.py:25-31), (OEF_k, DBV_k) =
+ * forward_transform(a_k, b_k) (model.py:299-305).
+ *   out [N][QBOLD_CAL_OUT]:
+ *     0 pit_oef = Phi((a* - mu_o) e^{-s_o})
+ *     1 pit_dbv = Phi((b* - mu_d) / sqrt(c^2 + e^{2 s_d}))
+ *     2 hpd     = -expm1(-d^2 / 2), d^2 = || L_q^-1 (u* - mu) ||^2: the level of the smallest highest-density ellipse of
+ *                 q that contains the truth
+ *     3 rank fraction of OEF: a_k against a* (the sigmoid is monotone)
+ *     4 rank fraction of DBV: b_k against b*
+ *     5 rank fraction of R2': OEF_k DBV_k against OEF* DBV* of the given truth (dw_coef > 0 cancels)
+ *   The rank fraction of a statistic d, without log_w: float(2 #{d_k < d*} + #{d_k == d*}) / float(2 L) -- integer
+ *   counts, one rounding; with log_w: sum_k w~_k ([d_k < d*] + [d_k == d*] / 2), w~ = exp(log_w - max) / sum exp(log_w -
+ *   max), float32 sums in a fixed order.
+ * Non-finite heads or truths propagate (a NaN one gives NaN, never rank 0); nothing is clamped but the unit-interval
+ * value above.  No sums, no workspace, no atomics: a voxel's outputs are the same bits at any batch position, under any
+ * sharding by voxel0 and from run to run.  QBOLD_ERR_INVALID for L < 1, L > QBOLD_CAL_MAX_L, N < 0, a NULL out, or a
+ * NULL theta_true / q when N > 0; N = 0 succeeds. */
+#define QBOLD_CAL_OUT 6
+#define QBOLD_CAL_MAX_L (1 << 20)
+int qbold_calibration(const qbold_ctx* ctx, const float* theta_true, const float* mask, const float* q,
+                      const float* log_w, const float* z, int L, uint64_t seed, int64_t voxel0, float* out,
+                      int64_t N, void* stream);
+
 /* ---- gradients (training) ------------------------------------------------------------------- */
 /* Adjoint of qbold_elbo_fwd with respect to the encoder's head outputs: what TensorFlow autodiff
  * yields through build_fine_tuner's sampling + fine_tune_loss_fn + kl_loss (model.py:239-286,

@@ -20,6 +20,8 @@ QBOLD_PSIS_MIN_K = 25     # qbold_psis: the draws per row a wave holds
 QBOLD_PSIS_MAX_K = 1024
 QBOLD_PSIS_MAX_C = 8
 QBOLD_LOO_OUT = 6     # columns of qbold_loo's out
+QBOLD_CAL_OUT = 6     # columns of qbold_calibration's out
+QBOLD_CAL_MAX_L = 1 << 20
 
 
 class QboldError(RuntimeError):
@@ -141,6 +143,7 @@ SIGNATURES = {
     "qbold_posterior_predictive": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
     "qbold_loo_workspace_bytes": (_I64, [_P, C.c_int, _I64]),
     "qbold_loo": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "qbold_calibration": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _I64, _P]),
     "qbold_refine_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(RefineCfg), _U64,
                                          _I64, _P, _P, _I64, _P]),
     "qbold_refine_spatial_workspace_bytes": (C.c_int64, [_P, C.POINTER(Geometry)]),

@@ -326,6 +326,55 @@ class FineTuner:
             sg = torch.full_like(sg, math.exp(self.log_sigma))
         return q, sg
 
+    def calibration(self, data, theta_true, mask=None, prior=None, no_samples=255, q=None, psis=False, seed=1, voxel0=0,
+                    bins=16, psis_chunk=None):
+        """Calibration of the posteriors against a KNOWN truth (Context.calibration; simulation-based calibration, Talts
+        et al. 2018): theta_true [..., 2] = the (OEF, DBV) that generated `data`, the heads q [..., 5] (None: the encoder
+        heads of encoder_model.predict; refine()'s output, say), `no_samples` = L draws per voxel -- the draws of
+        log_evidence() for the same seed and voxel0.  Returns dict(out [..., 6] = (pit_oef, pit_dbv, hpd, rank
+        fractions of OEF, DBV, R2'), khat (psis) or None, summary = calibration.summarise(out, L, bins): histograms,
+        uniformity chi-square and interval coverage).  Voxels outside the mask are NaN and not counted.
+        psis=True (needs `prior` and 25 <= no_samples <= 1024): the ranks are taken under the Pareto-smoothed importance
+        weights of those same draws (Context.log_evidence_draws + Context.psis(want_weights=True)), i.e. they test the
+        importance-corrected posterior instead of q; khat [...] is each voxel's k^ and the summary carries the table
+        restricted to khat below ops.psis_khat_threshold(L) as well.  Computed in voxel chunks by log_evidence(psis=True)'s
+        rule (per-draw buffers under 256 MiB, or psis_chunk voxels); chunks pass their own voxel0, so the result does
+        not depend on the chunking."""
+        from .calibration import summarise
+        tr = self._trainer
+        self._check_mvn_family("calibration")
+        L = int(no_samples)
+        if psis and not 25 <= L <= 1024:   # QBOLD_PSIS_MIN_K, QBOLD_PSIS_MAX_K
+            raise ValueError("calibration(psis=True) needs 25 <= no_samples <= 1024")
+        if psis and prior is None:
+            raise ValueError("calibration(psis=True) needs the prior the importance weights are taken against")
+        T = data.shape[-1]
+        x = _flat(data, T)
+        N = x.shape[0]
+        m = None if mask is None else mask.reshape(-1)
+        q, sg = self._heads_and_sigma(data, q)
+        th = _flat(torch.as_tensor(theta_true, device=x.device), 2).contiguous()
+        lead = data.shape[:-1]
+        khat = None
+        if not psis:
+            out = tr._ctx.calibration(th, q, m, L=L, seed=seed, voxel0=voxel0)
+        else:
+            p5 = _flat(prior, prior.shape[-1]).contiguous()
+            chunk = int(psis_chunk) if psis_chunk else max((256 << 20) // (16 * L) - 1, 1)
+            if chunk < 1:
+                raise ValueError("psis_chunk must be positive")
+            out = torch.empty((N, 6), dtype=torch.float32, device=x.device)
+            khat = torch.empty(N, dtype=torch.float32, device=x.device)
+            for a in range(0, N, chunk):
+                b = min(a + chunk, N)
+                mc = None if m is None else m[a:b]
+                lw, _ = tr._ctx.log_evidence_draws(x[a:b], mc, q[a:b], p5[a:b], sg[a:b], L, seed=seed, voxel0=voxel0 + a)
+                po, _, wts = tr._ctx.psis(lw, None, mc, want_weights=True)
+                khat[a:b] = po[:, 0]
+                out[a:b] = tr._ctx.calibration(th[a:b], q[a:b], mc, L=L, log_w=wts, seed=seed, voxel0=voxel0 + a)
+        summary = summarise(out, L, bins=bins, weighted=psis, khat=khat)
+        return dict(out=out.reshape(lead + (6,)), khat=None if khat is None else khat.reshape(lead), summary=summary)
+
     def refine(self, data, mask, prior, steps=200, no_samples=1, lr=0.1, lr_final=None, optimizer="adam",
                seed=1, voxel0=0, smoothness_weight=0.0):
         """Semi-amortised inference (Kim et al. 2018; Cremer et al. 2018): start from the encoder heads of
@@ -500,6 +549,8 @@ class EncoderTrainer:
         self._min_dbv = 0.001
         self._heteroscedastic_noise = heteroscedastic_noise
         self._predict_log_data = predict_log_data
+        self._full_model = full_model
+        self._use_blood = use_blood
         # Store the spin-echo index (model.py:95)
         self._se_idx = int(abs(float(system_params['tau_start']) / float(system_params['tau_step'])))
         self._seed = int(seed)
@@ -615,6 +666,41 @@ class EncoderTrainer:
         if return_stds:  # NB: biased variances under the name "stds" (model.py:331, Appendix B9)
             return means, var[:, :c].reshape(lead + (c,))
         return means
+
+    def calibration(self, model, n_voxels=65536, no_samples=255, seed=1, fine_tuner=None, prior=None, psis=False,
+                    use_first_op=False, uniform_prop=0.0, bins=16):
+        """Do the encoder's posteriors cover as often as they claim?  Simulates n_voxels voxels with known (OEF, DBV)
+        (training.synthetic_voxel_dataset: the pre-training priors, forward model and noise), takes the heads of stream 1
+        (use_first_op) or stream 2 and places each truth in its posterior (Context.calibration, `no_samples` draws per
+        voxel).  Returns FineTuner.calibration's dict(out [N, 6], khat, summary); the summary gains z_mean and z_rms of
+        (OEF, DBV, R2'): (posterior mean - truth) / posterior sd from Context.posterior_moments at `no_samples` draws,
+        0 and 1 for a calibrated posterior.
+        fine_tuner: score that fine tuner's model (its sigma; psis=True with a [N, 5] `prior` ranks under the
+        importance-corrected posterior); without one the heads go to Context.calibration directly."""
+        from .calibration import summarise
+        from .training import synthetic_voxel_dataset
+        if not self._use_mvg:
+            raise NotImplementedError("calibration works on the use_mvg=True family; the diagonal family draws with "
+                                      "exp(raw_s), not transform_std (model.py:696-698)")
+        if psis and fine_tuner is None:
+            raise ValueError("calibration(psis=True) needs the fine_tuner whose likelihood the weights are taken under")
+        cfg = dict(uniform_prop=uniform_prop, full_model=self._full_model, use_blood=self._use_blood)
+        x, mask, y = synthetic_voxel_dataset(self._system_params, cfg, int(n_voxels), self._ctx.device, seed)
+        o1, o2, _ = model.predict(x, want=("out1",) if use_first_op else ("out2",))
+        q = _flat((o1 if use_first_op else o2)[..., :5], 5).contiguous()
+        L = int(no_samples)
+        if fine_tuner is not None:
+            res = fine_tuner.calibration(x, y, mask, prior=prior, no_samples=L, q=q, psis=psis, seed=seed, bins=bins)
+        else:
+            out = self._ctx.calibration(y, q, mask, L=L, seed=seed)
+            res = dict(out=out, khat=None, summary=summarise(out, L, bins=bins))
+        means, var = self._ctx.posterior_moments(q, L, seed=seed)
+        truth = torch.cat([y, self.calculate_r2p(y[:, :1], y[:, 1:2])], 1)
+        zs = ((means - truth) / var.sqrt()).double()
+        zs = zs[torch.isfinite(zs).all(1)]
+        res["summary"]["z_mean"] = [float(v) for v in zs.mean(0)]
+        res["summary"]["z_rms"] = [float(v) for v in (zs * zs).mean(0).sqrt()]
+        return res
 
     def oef_dbv_metrics(self, y_true, y_pred, oef_dbv_r2p=0):
         means = self.calculate_means(y_pred, None, include_r2p=True)

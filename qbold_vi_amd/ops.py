@@ -563,6 +563,33 @@ class Context:
                                        _ptr(means), _ptr(weights), N, _stream()), "qbold_psis")
         return out, means, weights
 
+    def calibration(self, theta_true, q, mask=None, L=255, log_w=None, z=None, seed=1, voxel0=0):
+        """Where a known truth falls in each voxel's posterior (qbold_calibration): theta_true [N, 2] = (OEF, DBV), q
+        [N, 5] raw heads of the use_mvg family, L draws per voxel (the draws of log_evidence_draws for the same seed
+        and voxel0: Philox stream 6 unless z [N, L, 2] is given), log_w [N, L] = log-weights of those draws (psis'
+        `weights`, or raw log_w) or None.  Returns out [N, 6] = (pit_oef, pit_dbv, hpd, rank fractions of OEF, DBV,
+        R2'), each Uniform(0, 1) over voxels when q is calibrated; calibration.summarise turns it into histograms and
+        coverage.  Voxels with mask <= 0 are not read; their rows are NaN.  Runs on every context."""
+        th = _f32(theta_true, "theta_true", 2)
+        q = _f32(q, "q", 5)
+        N = q.numel() // 5
+        L = int(L)
+        if th.numel() != 2 * N:
+            raise ValueError("theta_true must be [N, 2]")
+        mask = _f32(mask, "mask") if mask is not None else None
+        if mask is not None and mask.numel() != N:
+            raise ValueError("mask must hold N values")
+        z = _f32(z, "z", 2) if z is not None else None
+        if z is not None and z.numel() != N * L * 2:
+            raise ValueError("z must be [N, L, 2]")
+        log_w = _f32(log_w, "log_w") if log_w is not None else None
+        if log_w is not None and log_w.numel() != N * L:
+            raise ValueError("log_w must be [N, L]")
+        out = torch.empty((N, _lib.QBOLD_CAL_OUT), dtype=torch.float32, device=q.device)
+        _lib.check(self.lib.qbold_calibration(self.handle, _ptr(th), _ptr(mask), _ptr(q), _ptr(log_w), _ptr(z), L,
+                                              int(seed), int(voxel0), _ptr(out), N, _stream()), "qbold_calibration")
+        return out
+
     def refine_posterior(self, x, mask, q, prior, sigma, steps=200, S=1, lr=0.1, lr_final=None, optimizer="adam",
                          betas=(0.9, 0.999), eps=1e-8, z=None, seed=1, voxel0=0, want_loss=False):
         """Semi-amortised refinement of each voxel's heads (qbold_refine_posterior): `steps` Adam or SGD steps on the

@@ -121,8 +121,27 @@ def main():
             f"psis(K={K},262144)": (lambda: ctx.psis(*ready(K), mq), (16 * K + 32) * f),
             f"log_evidence_draws+psis(K={K},262144)": (lambda: draws_psis(K), (8 * T + 76 + 32 * K) * f),
         }
+    # calibration against a known truth at L = 255 draws: the kernel regenerates the draws (28 bytes in, 24 out per voxel,
+    # 4 L more with weights), and beside it the path it replaces: the rows of log_evidence_draws (16 L bytes per voxel
+    # through HBM) compared in torch
+    cal_rows = {}
+
+    def cal_lw(L):   # the log-weights of L draws, dumped once
+        if L not in cal_rows:
+            cal_rows[L] = ctx.log_evidence_draws(x, mask, q, o1, sg, L, seed=1)[0]
+        return cal_rows[L]
+
+    def composed_ranks(L):
+        _, th = ctx.log_evidence_draws(x, mask, q, o1, sg, L, seed=1, want_theta=True)
+        d = torch.stack([th[..., 0], th[..., 1], th[..., 0] * th[..., 1]], -1)
+        t = torch.stack([y[:, 0], y[:, 1], y[:, 0] * y[:, 1]], -1)[:, None, :]
+        return (2 * (d < t).sum(1) + (d == t).sum(1)).float() / (2 * L)
     calls = {
         # name: (callable, algorithmic bytes per voxel)
+        "calibration(L=255)": (lambda: ctx.calibration(y, q, mask, L=255, seed=1), 28 + 24),
+        "calibration(L=255,log_w)": (lambda: ctx.calibration(y, q, mask, L=255, log_w=cal_lw(255), seed=1),
+                                     28 + 24 + 4 * 255),
+        "log_evidence_draws+torch_ranks(L=255)": (lambda: composed_ranks(255), 8 * T + 44 + 2 * 16 * 255),
         "signal_fwd": (lambda: ctx.signal_fwd(y), 8 + 4 * T),
         "signal_bwd": (lambda: ctx.signal_bwd(y, gs), 8 + 4 * T + 8),
         "signal_fwd_ex(hct)": (lambda: ctx.signal_fwd_ex(y, mask * 0.34), 12 + 4 * T),
