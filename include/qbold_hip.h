@@ -552,6 +552,72 @@ int qbold_posterior_grid(const qbold_ctx* ctx, const float* x, const float* mask
                          const float* sigma, const float* q, const qbold_grid_cfg* cfg, float* out, float* box,
                          double* sums, void* workspace, int64_t N, void* stream);
 
+/* Per-voxel Laplace posteriors of the fine-tuning model on any tau grid (this package's addition; the reference has no
+ * counterpart): the MAP of qbold_posterior_grid's log-joint by Levenberg-Marquardt on the logit plane -- the classical
+ * per-voxel non-linear least-squares fit, with the prior as two more residual rows -- and the Gauss-Newton (Fisher)
+ * curvature there, returned as numbers and as five raw heads that every entry taking q accepts.  No encoder is involved.
+ *   Model (qbold_posterior_grid's): u = (a, b), the logits of (OEF, DBV), kept within +-13.8155; sigma fixed.
+ *     F(u) = 1/2 (sum_t r_t^2 + |w|^2),  r_t = (y_t - yh_t(u)) / sigma_t,  w = L_p^-1 (u - mu_p)
+ *     y, yh: data and prediction, each divided by its own spin-echo image (the mean of three with multi-image
+ *     normalisation) + 1e-3, as qbold_elbo_bwd forms them; (mu_p, L_p) = make_mvn of prior[5].  So
+ *     -F = J - (-sum_t log sigma_t - (T/2) log 2 pi - log 2 pi - log det L_p), J the grid entry's log-joint.
+ *   A = J^T J, the 2 x 2 Gauss-Newton matrix over the T + 2 residual rows (positive definite through the prior rows),
+ *   g = J^T r, dec(u) = sqrt(g^T A^-1 g): the Newton decrement, the distance to the stationary point in posterior sds.
+ *   J is the derivative of the r that is evaluated: the tissue table drops Simpson node 0 from F (as the reference's
+ *   float32 value does) and J takes the table's own slope, without that node's -- unlike qbold_elbo_bwd, which restates
+ *   the reference's autodiff gradient and keeps it (qbold_ctx_set_grad_node0 has no effect here).
+ *   Schedule.  Start u_0 = clip(u0 row), or clip(mu_p) when u0 is NULL; lambda = lambda0.  The start point is evaluated
+ *   and accepted (iterations = 0; a voxel with dec(u_0) < tol stops there).  Then at most max_iter iterations, each one
+ *   evaluation of (F, g, A) at the trial point
+ *       u' = clip(u + delta),  delta = -(A + lambda diag A)^-1 g   (A, g at the last accepted point u):
+ *     with dF = F(u) - F(u'), except that when |F(u) - F(u')| <= band
+ *         dF = -1/2 (g(u) + g(u'))^T (u' - u)   [the tie rule: the trapezoid rule on the two gradients, exact for a
+ *         quadratic F], band = max(band(u), band(u')), band(v) = 2^-22 (sum_t |r_t| yh_t / sigma_t + F) at v: what
+ *         two float32 roundings of every yh_t move F by, to first order.  Within it float32 cannot order the two
+ *         values of F, while the gradients keep their digits.
+ *     dF > 0: accepted, u <- u'.  The voxel has converged and stops when dec(u) < tol.  Then [the gain rule]
+ *         lambda <- max(lambda * (1 / lambda_down), 1e-7) when dF >= 0.25 pred, pred = -g^T d - 1/2 d^T A d the
+ *         quadratic model's reduction along the step d = u' - u actually taken; lambda <- min(lambda * lambda_up, 1e7)
+ *         otherwise: the step is kept but the damping raised.  Gauss-Newton leaves out the residuals' curvature; on a
+ *         weakly determined voxel its full step overshoots about twofold along the soft direction, F still falls a
+ *         little every time, and without this rule lambda only shrinks while the iterates zig-zag across the valley
+ *         past max_iter (MEASUREMENTS.md section 27).
+ *     otherwise (a non-finite F(u') included): rejected, lambda <- min(lambda * lambda_up, 1e7).
+ *     Deviations from the plain accept-if-lower schedule: the tie rule, the gain rule, the bracket [1e-7, 1e7] of
+ *     lambda, and the division by lambda_down as a multiplication by its float32 reciprocal.
+ *   Defaults: max_iter 50, lambda0 1e-2, lambda_up 10, lambda_down 3, tol 1e-3.
+ *   u0 [N][2] or NULL.  sigma [N][T]: the exponentiated sigma, as qbold_elbo_fwd takes it.
+ *   out [N][QBOLD_LAPLACE_OUT], everything at the last accepted point u^, Sigma = A^-1 there:
+ *      0-1  a^, b^
+ *      2-4  OEF, DBV, R2' = dw_coef OEF DBV at u^
+ *      5-7  sd_a, sd_b, corr of Sigma
+ *      8-10 delta-method sds of OEF, DBV, R2' (the transforms' slopes at u^ through Sigma)
+ *      11   log p^ = J(u^) + log 2 pi - 1/2 log det A: the Laplace evidence, comparable with qbold_posterior_grid's log_p
+ *      12   chi2 = sum_t r_t^2 at u^
+ *      13   iterations used (trial points after the start point)
+ *      14   flags, as a float: bit 0 = not converged within max_iter, bit 1 = a coordinate of u^ sits on the clip,
+ *           bit 2 = heads clamped
+ *   q_out [N][5]: raw heads whose make_mvn is (u^, the Cholesky factor of Sigma): e^(2 s_o) = Sigma_aa,
+ *     c = Sigma_ab / e^(s_o), e^(2 s_d) = Sigma_bb - c^2, through the inverses of transform_std / transform_offdiag.  Those
+ *     reach s in (-4, 2) and |c| < e^-2 only; each tanh is clamped to |tanh(raw)| <= 1 - 1e-6, i.e. s to
+ *     [-4 + 3e-6, 2 - 3e-6] and |c| to (1 - 1e-6) e^-2, and e^(2 s_d) is formed with the c that is stored, so that the
+ *     marginal variance of b survives a clamped c.  Any clamp sets bit 2; out keeps the unclamped Sigma.
+ *   Voxels with mask <= 0 (or NaN) are not evaluated: a NaN row in out, the prior row copied bit for bit to q_out; mask
+ *   NULL evaluates every voxel.  No random stream, no atomics, no sums, no workspace: a voxel's outputs are the same
+ *   bits in any batch at any position, whatever shares its wave.  One run-time-T kernel serves every 1 <= T <= 64.
+ * Full signal model in table mode, Gaussian likelihood on linear data, either normalisation, any spin-echo index;
+ * QBOLD_ERR_UNSUPPORTED otherwise (literal tissue mode, Student-t, log data, no full model).  QBOLD_ERR_INVALID for
+ * max_iter < 1, a non-positive or non-finite lambda0 or tol, lambda_up <= 1 or lambda_down <= 1 (or non-finite), N < 0
+ * or a NULL required buffer (cfg, q_out, out; x, prior, sigma when N > 0); these are checked first. */
+typedef struct {
+    int max_iter;
+    float lambda0, lambda_up, lambda_down, tol;
+} qbold_laplace_cfg;
+#define QBOLD_LAPLACE_OUT 15
+int qbold_laplace_posterior(const qbold_ctx* ctx, const float* x, const float* mask, const float* prior,
+                            const float* sigma, const float* u0, const qbold_laplace_cfg* cfg,
+                            float* q_out, float* out, int64_t N, void* stream);
+
 /* Posterior predictive checks of the fine-tuning model per voxel (this package's addition; the reference has no
  * counterpart): Gelman, Meng & Stern 1996 for the p-value, Watanabe 2010 / Vehtari, Gelman & Gabry 2017 for lppd and
  * WAIC.  theta_l, l = 0 .. L-1: the reparameterised draws of q (heads [N][5], the use_mvg = True family), from explicit

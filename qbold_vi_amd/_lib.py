@@ -22,6 +22,7 @@ QBOLD_PSIS_MAX_C = 8
 QBOLD_LOO_OUT = 6     # columns of qbold_loo's out
 QBOLD_CAL_OUT = 6     # columns of qbold_calibration's out
 QBOLD_CAL_MAX_L = 1 << 20
+QBOLD_LAPLACE_OUT = 15   # columns of qbold_laplace_posterior's out
 
 
 class QboldError(RuntimeError):
@@ -58,6 +59,12 @@ class GridCfg(C.Structure):
     """qbold_grid_cfg: grid sides, locate passes, Gauss-Hermite order, start-box span, keep cut, quantile levels."""
     _fields_ = [("coarse", C.c_int32), ("fine", C.c_int32), ("locate", C.c_int32), ("gh", C.c_int32),
                 ("span", C.c_float), ("cut", C.c_float), ("level_lo", C.c_float), ("level_hi", C.c_float)]
+
+
+class LaplaceCfg(C.Structure):
+    """qbold_laplace_cfg: the Levenberg-Marquardt schedule of qbold_laplace_posterior."""
+    _fields_ = [("max_iter", C.c_int32), ("lambda0", C.c_float), ("lambda_up", C.c_float), ("lambda_down", C.c_float),
+                ("tol", C.c_float)]
 
 
 class Geometry(C.Structure):
@@ -140,6 +147,7 @@ SIGNATURES = {
     "qbold_log_evidence_draws": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _I64, _P]),
     "qbold_psis": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _I64, _P]),
     "qbold_posterior_grid": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GridCfg), _P, _P, _P, _P, _I64, _P]),
+    "qbold_laplace_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(LaplaceCfg), _P, _P, _I64, _P]),
     "qbold_posterior_predictive": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
     "qbold_loo_workspace_bytes": (_I64, [_P, C.c_int, _I64]),
     "qbold_loo": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _P, _P, _I64, _P]),

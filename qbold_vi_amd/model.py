@@ -440,6 +440,39 @@ class FineTuner:
                     box=None if box is None else box.reshape(lead + (4,)), sums=sums, mean_log_evidence=lp,
                     mean_elbo=el, mean_gap=gap)
 
+    def laplace(self, data, mask, prior, start="prior", **cfg):
+        """Per-voxel Laplace posteriors on any tau grid (Context.laplace_posterior; cfg: max_iter, tol, lambda0,
+        lambda_up, lambda_down): the MAP of the log-joint by Levenberg-Marquardt -- the classical non-linear
+        least-squares fit under the prior -- and the Gauss-Newton curvature there, with the sigma refine() takes (the
+        encoder's sigma head or the fine tuner's homoscedastic sigma).  start = "prior": from the prior mean;
+        "encoder": from the encoder heads' means.  Shaped like the data's spatial dims:
+          q [..., 5] (raw heads of N(u^, A^-1): goes unchanged to calculate_means, elbo(q=...), log_evidence(q=...),
+            posterior_grid(q=...), posterior_predictive(q=...), loo, calibration), map [..., 2] (logits a^, b^)
+          oef, dbv, r2p at the MAP and oef_sd, dbv_sd, r2p_sd (delta method), logit_sd [..., 2], corr
+          log_evidence (Laplace), chi2, iterations, converged, on_clip, clamped (bool; clamped: the heads could not
+            hold the covariance exactly)
+        Voxels outside the mask are NaN (False in the flags) and keep the prior's row in q."""
+        tr = self._trainer
+        self._check_mvn_family("laplace")
+        if start not in ("prior", "encoder"):
+            raise ValueError("laplace: start must be 'prior' or 'encoder'")
+        T = data.shape[-1]
+        x = _flat(data, T)
+        m = None if mask is None else mask.reshape(-1)
+        p5 = _flat(prior, prior.shape[-1]).contiguous()
+        q, sg = self._heads_and_sigma(data)
+        u0 = q[:, [0, 2]].contiguous() if start == "encoder" else None
+        q_out, out = tr._ctx.laplace_posterior(x, m, p5, sg, u0=u0, **cfg)
+        lead = data.shape[:-1]
+        col = lambda i: out[:, i].reshape(lead)   # noqa: E731
+        flags = torch.nan_to_num(out[:, 14], nan=0.0).to(torch.int32)
+        live = ~torch.isnan(out[:, 14])
+        bit = lambda b: (((flags >> b) & 1) == 1).reshape(lead)   # noqa: E731
+        return dict(q=q_out.reshape(lead + (5,)), map=out[:, 0:2].reshape(lead + (2,)), oef=col(2), dbv=col(3),
+                    r2p=col(4), logit_sd=out[:, 5:7].reshape(lead + (2,)), corr=col(7), oef_sd=col(8), dbv_sd=col(9),
+                    r2p_sd=col(10), log_evidence=col(11), chi2=col(12), iterations=col(13),
+                    converged=(live & ((flags & 1) == 0)).reshape(lead), on_clip=bit(1), clamped=bit(2))
+
     def posterior_predictive(self, data, mask, q=None, no_samples=256, seed=1, voxel0=0, want_curves=False):
         """Posterior predictive checks of `no_samples` = L draws per voxel (Context.posterior_predictive) for the heads q
         [..., 5] (None: the encoder heads of encoder_model.predict; refine()'s output, say) and the sigma that goes with
@@ -888,7 +921,7 @@ class EncoderTrainer:
     def save_predictions(self, model, data, filename, transform_directory=None, use_first_op=True,
                          fine_tuner_model=None, priors=None, iw_samples=None, refine_steps=None,
                          posterior_grid=None, ppc_samples=None, refine_smoothness_weight=0.0, psis=False,
-                         loo_samples=None):
+                         loo_samples=None, laplace=False):
         """model.py:772-887: write `<filename>_{oef,dbv,r2p,logstds}.nii.gz` (posterior means of
         OEF / DBV / R2' over 200 draws and their variances) and, with a fine tuner,
         `_likelihood` (per-voxel NLL averaged over 100 stochastic passes), `_kl` (100-draw KL to
@@ -920,12 +953,19 @@ class EncoderTrainer:
         cross-validation of K draws from the encoder's heads (FineTuner.loo) as `_elpdloo`, `_ploo`, `_khatloo` (the
         largest Pareto k^ over the tau images) and `_worsttau` (its tau index), NaN outside the mask; these maps join the
         returned dict.  None writes nothing new.
+        laplace = True or a dict of FineTuner.laplace keywords (with a fine tuner; this package's addition, default
+        off): the per-voxel Laplace posterior (Levenberg-Marquardt MAP fit under the prior, any tau grid) as
+        `_oef_laplace`, `_dbv_laplace`, `_r2p_laplace`, `_oefsd_laplace`, `_dbvsd_laplace`, `_logevidence_laplace`,
+        `_chi2` and `_laplaceflags` (bit 0 not converged, bit 1 on the logit clip, bit 2 heads clamped), zero outside
+        the mask; these maps join the returned dict.
         data [subj, X, Y, Z, T+1] with the mask last; each map is stored as [X, Y, Z, subj*C].
         `transform_directory/example.nii.gz`, when present, donates its header (:794-797); the
         FSL `applywarp`/`fslmerge` MNI step (:850-879) is preprocessing outside this package and
         is skipped."""
         import os
         from . import nifti
+        if laplace and not fine_tuner_model:
+            raise ValueError("save_predictions(laplace=True) needs a fine tuner (its sigma and the prior maps)")
         data = torch.as_tensor(data, dtype=torch.float32, device=self._ctx.device)
         T = self._ctx.T
         mask = data[..., -1:]
@@ -1049,6 +1089,21 @@ class EncoderTrainer:
             for k, v in loo_maps.items():
                 save_im_data(v, filename + '_' + k)
             iw_maps = dict(iw_maps or {}, **loo_maps)
+
+        if fine_tuner_model and laplace:
+            kw = dict(laplace) if isinstance(laplace, dict) else {}
+            lp = fine_tuner_model.laplace(data[..., :-1], mask,
+                                          torch.as_tensor(priors, device=data.device)[..., :self._nq], **kw)
+            live = mask[..., 0] > 0
+            zero = torch.zeros_like(lp["oef"])
+            flags = (~lp["converged"]).float() + 2.0 * lp["on_clip"].float() + 4.0 * lp["clamped"].float()
+            lap_maps = {k: torch.where(live, v, zero)[..., None] for k, v in
+                        (("oef_laplace", lp["oef"]), ("dbv_laplace", lp["dbv"]), ("r2p_laplace", lp["r2p"]),
+                         ("oefsd_laplace", lp["oef_sd"]), ("dbvsd_laplace", lp["dbv_sd"]),
+                         ("logevidence_laplace", lp["log_evidence"]), ("chi2", lp["chi2"]), ("laplaceflags", flags))}
+            for k, v in lap_maps.items():
+                save_im_data(v, filename + '_' + k)
+            iw_maps = dict(iw_maps or {}, **lap_maps)
 
         save_im_data(means[..., 0:1], filename + '_oef')
         save_im_data(means[..., 1:2], filename + '_dbv')

@@ -56,6 +56,19 @@ def _refine_cfg(what, steps, S, lr, lr_final, optimizer, betas, eps):
     return steps, S, Sp, cfg
 
 
+def _laplace_cfg(what, max_iter, tol, lambda0, lambda_up, lambda_down):
+    """The argument checks of laplace_posterior (raised before any launch): qbold_laplace_cfg."""
+    max_iter = int(max_iter)
+    tol, lambda0, lambda_up, lambda_down = float(tol), float(lambda0), float(lambda_up), float(lambda_down)
+    if max_iter < 1:
+        raise ValueError(f"{what}: need max_iter >= 1")
+    if not (0.0 < tol < math.inf and 0.0 < lambda0 < math.inf):
+        raise ValueError(f"{what}: tol and lambda0 must be positive and finite")
+    if not (1.0 < lambda_up < math.inf and 1.0 < lambda_down < math.inf):
+        raise ValueError(f"{what}: need finite lambda_up > 1 and lambda_down > 1")
+    return _lib.LaplaceCfg(max_iter, lambda0, lambda_up, lambda_down, tol)
+
+
 def merge_ranges(pieces):
     """Sorted [offset, length] pieces with touching neighbours merged."""
     out = []
@@ -709,7 +722,40 @@ class Context:
                    "qbold_posterior_grid")
         return sums, out, box
 
-    PPC_COLUMNS = ("ppp", "dbar", "lppd", "p_waic", "elpd_waic", "max_abs_z")
+    LAPLACE_COLUMNS = ("a", "b", "oef", "dbv", "r2p", "sd_a", "sd_b", "corr", "oef_sd", "dbv_sd", "r2p_sd",
+                       "log_evidence", "chi2", "iterations", "flags")
+
+    def laplace_posterior(self, x, mask, prior, sigma, u0=None, max_iter=50, tol=1e-3, lambda0=1e-2, lambda_up=10.0,
+                          lambda_down=3.0):
+        """Per-voxel Laplace posteriors on any tau grid (qbold_laplace_posterior): the MAP of the log-joint on the
+        logit plane by Levenberg-Marquardt from u0 [N, 2] (None: the prior mean), stopped where the Newton decrement
+        falls below `tol` or after `max_iter` iterations, and the Gauss-Newton curvature there.  Voxels with mask <= 0
+        come back NaN in out and with the prior's row in q_out.
+        Returns (q_out [N, 5] raw heads of N(u^, A^-1), for every entry that takes q; out [N, 15] with the columns of
+        LAPLACE_COLUMNS)."""
+        cfg = _laplace_cfg("laplace_posterior", max_iter, tol, lambda0, lambda_up, lambda_down)
+        for name, t in (("x", x), ("prior", prior), ("sigma", sigma), ("mask", mask), ("u0", u0)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+                raise ValueError(f"laplace_posterior: {name} must be a cuda (ROCm) tensor; there is no CPU fallback")
+        x = _f32(x, "x", self.T)
+        N = x.numel() // self.T
+        prior = _f32(prior, "prior", 5)
+        sigma = _f32(sigma, "sigma", self.T)
+        mask = _f32(mask, "mask") if mask is not None else None
+        u0 = _f32(u0, "u0", 2) if u0 is not None else None
+        for name, t, w in (("prior", prior, 5), ("sigma", sigma, self.T), ("mask", mask, 1), ("u0", u0, 2)):
+            if t is not None and t.numel() != N * w:
+                raise ValueError(f"laplace_posterior: {name} does not match x ({N} voxels)")
+        q_out = torch.empty((N, 5), dtype=torch.float32, device=x.device)
+        out = torch.empty((N, _lib.QBOLD_LAPLACE_OUT), dtype=torch.float32, device=x.device)
+        if N == 0:   # empty tensors have no address to pass
+            return q_out, out
+        _lib.check(self.lib.qbold_laplace_posterior(self.handle, _ptr(x), _ptr(mask), _ptr(prior), _ptr(sigma),
+                                                    _ptr(u0), C.byref(cfg), _ptr(q_out), _ptr(out), N, _stream()),
+                   "qbold_laplace_posterior")
+        return q_out, out
+
+    PPC_COLUMNS =("ppp", "dbar", "lppd", "p_waic", "elpd_waic", "max_abs_z")
 
     def posterior_predictive(self, x, mask, q, sigma, L=256, z=None, seed=1, voxel0=0, want_curves=False):
         """Posterior predictive checks of L draws per voxel from q (qbold_posterior_predictive; Philox stream 8 unless

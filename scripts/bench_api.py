@@ -16,6 +16,10 @@ from qbold_vi_amd.init import init_encoder_weights  # noqa: E402
 from qbold_vi_amd.ops import Context, EncoderWeights, TrainState  # noqa: E402
 
 
+def only_names():
+    return [a for a in sys.argv[1:] if not a.startswith("-")]   # name substrings: time only the matching calls
+
+
 def main():
     cfg = configparser.ConfigParser()
     cfg.read(os.path.join(ROOT, "config"))
@@ -218,7 +222,31 @@ def main():
     }
     calls.update(psis_rows(64))
     calls.update(psis_rows(256))
-    only = [a for a in sys.argv[1:] if not a.startswith("-")]   # name substrings: time only the matching calls
+    # Laplace posteriors (Levenberg-Marquardt MAP + curvature) at the defaults from the prior mean, on noisy synthetic
+    # voxels (noise sd 0.02 of the spin-echo image, sigma = 0.02, one prior for all: OEF 0.4, DBV 0.03, sd 0.6 logits),
+    # beside the only other route to a MAP and a covariance on every T, posterior_grid at its defaults on the same
+    # voxels.  Bytes: x, sigma, prior, mask in; q_out, out (and the grid's out) back.
+    lap_info = {}
+
+    def laplace_rows(name, p):
+        c = Context(p, True, True)
+        xs = c.signal_fwd(y)
+        xs = xs + 0.02 * xs[:, c.se_idx:c.se_idx + 1] * torch.randn(xs.shape, generator=g, device="cuda")
+        sgs = torch.full((n, c.T), 0.02, device="cuda")
+        pl = torch.tensor([-0.2007, 0.1634, -1.7750, 0.1634, 0.0], device="cuda").repeat(n, 1)
+
+        def lap():
+            q_l, o_l = c.laplace_posterior(xs, mask, pl, sgs)
+            lap_info[f"laplace(T={name})"] = o_l
+            return q_l
+        return {f"laplace(T={name})": (lap, 8 * c.T + 24 + 20 + 60),
+                f"posterior_grid(T={name},q=None)": (lambda: c.posterior_grid(xs, mask, pl, sgs), 8 * c.T + 24 + 68)}
+    if not only_names() or any("laplace" in o or "posterior_grid(T=" in o for o in only_names()):
+        calls.update(laplace_rows("11", params))
+        calls.update(laplace_rows("24", dict(params, tau_start="-0.028", tau_end="0.065", tau_step="0.004")))
+        calls.update(laplace_rows("33", dict(params, tau_start="-0.008", tau_end="0.057", tau_step="0.002")))
+        calls.update(laplace_rows("64", dict(params, tau_start="-0.008", tau_end="0.0555", tau_step="0.001")))
+    only = only_names()
     out = {}
     for name, (fn, bpv) in calls.items():
         if only and not any(o in name for o in only):
@@ -239,6 +267,11 @@ def main():
         out[name] = {"ms": round(ms, 4)}
         if bpv:
             out[name]["algorithmic_GBps"] = round(bpv * n / ms / 1e6, 1)
+        if name in lap_info:   # what the timed call did: iterations per voxel, the share that converged
+            o_l = lap_info[name]
+            out[name]["mean_iterations"] = round(o_l[:, 13].mean().item(), 3)
+            out[name]["max_iterations"] = int(o_l[:, 13].max().item())
+            out[name]["converged"] = round(((o_l[:, 14].int() & 1) == 0).float().mean().item(), 6)
     print(json.dumps({"voxels": n, "T": T, "calls": out}, indent=1))
 
 
