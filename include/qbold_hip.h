@@ -206,6 +206,17 @@ int64_t qbold_encoder_packed_floats(const qbold_encoder_shape* shape);
 /* Re-order the canonical blob into the LDS image the kernels stage (call after every update). */
 int qbold_encoder_pack(const qbold_ctx* ctx, const qbold_encoder_shape* shape,
                        const float* weights, float* packed, void* stream);
+/* The folded gate ops qbold_vi_fwd_folded reads beside the image (U <= 64 shapes): per block one dense op in the
+ * layout of the image's ops -- 4096 floats of A fragments [k-step][m][hi, lo][lane][8 halves], 64 floats of bias
+ * [m][group][reg] -- holding  A = -log2(e) (Wr2 Wg)  and  bias = -log2(e) (br2 Wg + bg + gate_offset)  (centre tap
+ * of Wr2 when spatial_taps == 9; a shared gate broadcast to all units; rows >= U zero).  The product is formed in
+ * float64, rounded once to float32 and split into f16 halves like every weight (whatever shape->precision says: the
+ * folded kernels are built for the split-f16 encoder only).  Behind the L ops: one flag
+ * float (0, or the largest folded weight beyond the f16 operand range) and padding to a multiple of 4 floats.
+ * qbold_encoder_gatefold_floats: the buffer's size in floats.  Pack after every weight update, as the image. */
+int64_t qbold_encoder_gatefold_floats(const qbold_encoder_shape* shape);
+int qbold_encoder_pack_gatefold(const qbold_ctx* ctx, const qbold_encoder_shape* shape,
+                                const float* weights, float* fold, void* stream);
 /* create_encoder forward, voxel-wise (model.py:97-113 normalise_data, :122-223):
  * x [N][T] -> out1 [N][5] (stream 1), out2 [N][5] (stream 2), sigma [N][T]; any may be NULL. */
 int qbold_encoder_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* shape, const float* packed,
@@ -369,6 +380,20 @@ int qbold_vi_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* shape, const f
                  const float* x, const float* mask, const float* prior, int S, int K, uint64_t seed,
                  int64_t voxel0, float* q_out, float* nll_kl, double* sums, void* workspace,
                  int64_t N, void* stream);
+/* qbold_vi_fwd with the gate logits of the gated residual blocks taken from relu(t) through the product matrix:
+ * gl = Wg r + bg + gate_offset with r = Wr2 relu(t) + br2 is gl = (Wr2 Wg) relu(t) + (br2 Wg + bg + gate_offset), so
+ * the kernels read `gate_fold` (qbold_encoder_pack_gatefold: that product, formed once per weight update) beside
+ * `packed` and split no second operand per block.  Same contract, same operand-range rule (a folded weight beyond
+ * 65504 poisons every voxel, as a weight of the image does); outputs agree with qbold_vi_fwd's to float32 rounding of
+ * the product, not bit for bit.  The folded kernels are built for the per-tau-table fast path (T = 11 or 24, L <= 2,
+ * table mode, Gaussian likelihood, the protocol's own spin echo, one-image normalisation) with the split-f16 encoder;
+ * on every other shape or context, and for QBOLD_ENC_BF16 (rounded to bf16 the product matrix would be another
+ * arithmetic than qbold_encoder_fwd's, 1e-3 apart on q), this IS qbold_vi_fwd on `packed` and `gate_fold` is not read
+ * (it must still be non-NULL).  gate_fold: 16-byte aligned. */
+int qbold_vi_fwd_folded(const qbold_ctx* ctx, const qbold_encoder_shape* shape, const float* packed,
+                        const float* gate_fold, const float* x, const float* mask, const float* prior, int S, int K,
+                        uint64_t seed, int64_t voxel0, float* q_out, float* nll_kl, double* sums, void* workspace,
+                        int64_t N, void* stream);
 
 /* Importance-weighted evidence (Burda et al. 2016) of the fine-tuning model (model.py:239-286, 527-568, 592-610):
  * per voxel K draws z_k ~ q, log w_k = -nll(x|z_k) - log q(z_k) + log prior(z_k) on the SAME draw.

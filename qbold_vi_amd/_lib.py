@@ -159,6 +159,10 @@ SIGNATURES = {
                                                  C.c_int, C.POINTER(RefineCfg), _U64, _I64, _P, _P, _P, _P]),
     "qbold_vi_fwd": (C.c_int, [_P, C.POINTER(EncoderShape), _P, _P, _P, _P, C.c_int, C.c_int,
                                _U64, _I64, _P, _P, _P, _P, _I64, _P]),
+    "qbold_encoder_gatefold_floats": (_I64, [C.POINTER(EncoderShape)]),
+    "qbold_encoder_pack_gatefold": (C.c_int, [_P, C.POINTER(EncoderShape), _P, _P, _P]),
+    "qbold_vi_fwd_folded": (C.c_int, [_P, C.POINTER(EncoderShape), _P, _P, _P, _P, _P, C.c_int, C.c_int,
+                                      _U64, _I64, _P, _P, _P, _P, _I64, _P]),
 }
 
 _lib = None

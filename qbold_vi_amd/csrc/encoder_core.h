@@ -111,6 +111,43 @@ __device__ __forceinline__ void copy_to_lds(float* __restrict__ dst, const float
     }
 }
 
+// The same copy with each block's gate slot (the last 4160 floats of a block: Wg's fragments and bias) taken from the
+// folded gate ops of qbold_encoder_pack_gatefold instead, [L][4160] floats and then the fold's own flag slot.  The
+// image's flag slot receives the larger of the two flags, so that the range guard starts from both.  One pass, one
+// writer per LDS address: no barrier beyond the one the plain copy needs.
+template <int THREADS, int FLAG, int BLK0, int NL>
+__device__ __forceinline__ void copy_to_lds_fold(float* __restrict__ dst, const float* __restrict__ src,
+                                                 const float* __restrict__ fold, int n4) {
+    static_assert(BLK0 % 4 == 0 && BLK_G_A % 4 == 0 && BLK_FLOATS % 4 == 0, "gate slots on float4 boundaries");
+    constexpr int kOp = BLK_FLOATS - BLK_G_A;   // floats per folded op
+    float4* d4 = reinterpret_cast<float4*>(dst);
+    const float fold_flag = fold[NL * kOp];
+    for (int base = 0; base < n4; base += 8 * THREADS) {
+        float4 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int p = base + u * THREADS + (int)threadIdx.x;
+            const int f = 4 * (p < n4 ? p : n4 - 1);
+            const float* from = src + f;
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                const int o = f - (BLK0 + l * BLK_FLOATS + BLK_G_A);
+                if (o >= 0 && o < kOp) from = fold + l * kOp + o;
+            }
+            v[u] = *reinterpret_cast<const float4*>(from);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int p = base + u * THREADS + (int)threadIdx.x;
+            if (p == FLAG / 4) {
+                float& c = FLAG % 4 == 0 ? v[u].x : FLAG % 4 == 1 ? v[u].y : FLAG % 4 == 2 ? v[u].z : v[u].w;
+                c = fmaxf(c, fold_flag);
+            }
+            if (p < n4) d4[p] = v[u];
+        }
+    }
+}
+
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
@@ -373,11 +410,63 @@ __device__ __forceinline__ ActFrag relu_frag(const ActFrag& f) {
     return o;
 }
 
+// The tail of a FOLD block (block_stream2): r = Wr2 f + br2 and y = -log2(e) x the gate logits (the folded op in the
+// block's gate slot) from ONE set of fragments f = frags(relu t), one 16-unit output tile at a time, each tile blended
+// into b as it finishes: b = skip (1 - g) + r g with g = sigmoid(logits) = rcp(1 + exp2(y)).  Neither r nor y is ever
+// whole in registers (16 VGPRs fewer at the block's peak than two dense_f16x3 calls), and the MFMAs of a tile's two
+// products are independent of each other.  Each accumulator takes its k-steps and its passes in dense_f16x3's order, so r
+// is the bits dense_f16x3 gives.  Fragments are fetched one step ahead, as there.  Split-f16 only.
+__device__ __forceinline__ void gate_blend_f16x3(const float* __restrict__ W, const f16x8 (&bhi)[2],
+                                                 const f16x8 (&blo)[2], const f32x4 (&skip)[4], f32x4 (&b)[4],
+                                                 int lane) {
+    const int g = lane >> 4;
+    // step n = (m, s, op): op 0 = Wr2, 1 = the folded gate op; fragment pair (s, m) of that op
+    auto frag = [&](int n, int part) {
+        const int m = n >> 2, s = (n >> 1) & 1, op = n & 1;
+        return lds_frag(W + (op ? BLK_G_A : BLK_R2_A), (s * 4 + m) * 2 + part, lane);
+    };
+    f16x8 whi = frag(0, 0), wlo = frag(0, 1);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        f32x4 acc[2] = {load4(W + BLK_R2_B + m * 16 + g * 4), load4(W + BLK_G_B + m * 16 + g * 4)};
+        f32x4 cross[2] = {f32x4{0.0f, 0.0f, 0.0f, 0.0f}, f32x4{0.0f, 0.0f, 0.0f, 0.0f}};
+        __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+        for (int n = 4 * m; n < 4 * m + 4; ++n) {
+            const int s = (n >> 1) & 1, op = n & 1;
+            f16x8 nhi = whi, nlo = wlo;
+            if (n + 1 < 16) {
+                nhi = frag(n + 1, 0);
+                nlo = frag(n + 1, 1);
+            }
+            acc[op] = QB_MFMA_F16(whi, bhi[s], acc[op]);
+            cross[op] = QB_MFMA_F16(whi, blo[s], cross[op]);
+            cross[op] = QB_MFMA_F16(wlo, bhi[s], cross[op]);
+            __builtin_amdgcn_sched_barrier(0);
+            whi = nhi;
+            wlo = nlo;
+        }
+        __builtin_amdgcn_s_setprio(QB_ENC_BASE_PRIO);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float r = fmaf(cross[0][k], QB_LO_UNSCALE, acc[0][k]);
+            const float y = fmaf(cross[1][k], QB_LO_UNSCALE, acc[1][k]);
+            const float gate = rcpf_(1.0f + exp2f_(y));             // model.py:169
+            b[m][k] = fmaf(gate, r - skip[m][k], skip[m][k]);       // skip (1 - g) + r g, model.py:170
+        }
+    }
+}
+
 // One create_block step of stream 2 (gated residual), in place -- model.py:147-172.
 // NONNEG: every b[m][k] is >= 0 on entry (block 0: dense_first ends in relu4), so the activation before the first
 // 3x3x1 conv is the identity and that conv takes the very fragments the shared conv just used.  Otherwise the
 // split-f16 path derives relu(b)'s fragments from b's (relu_frag); bf16 fragments are split again from relu4(b).
-template <bool BF = false, bool NONNEG = false>
+// FOLD (the fused inference kernels of vi_kernels.hip): the block's gate slot holds the folded op of
+// qbold_encoder_pack_gatefold, -log2(e) (Wr2 Wg) and -log2(e) (br2 Wg + bg + gate_offset), instead of Wg.  The gate
+// logits are affine in relu(t), so they come from the very fragments the Wr2 product takes: r is never split (no
+// second operand split, no range guard on r -- only what is split is guarded), the two products do not wait for each
+// other, and the sigmoid is rcp(1 + exp2(y)) on y = -log2(e) logits.
+template <bool BF = false, bool NONNEG = false, bool FOLD = false>
 __device__ __forceinline__ void block_stream2(const float* __restrict__ W, f32x4 (&b)[4],
                                               int lane, float* amax = nullptr) {
     f32x4 skip[4], t[4], r[4];
@@ -398,6 +487,12 @@ __device__ __forceinline__ void block_stream2(const float* __restrict__ W, f32x4
     }
 #pragma unroll
     for (int m = 0; m < 4; ++m) t[m] = relu4(t[m]);   // :155
+    if constexpr (FOLD) {
+        static_assert(!FOLD || !BF, "the folded gate ops: split-f16 encoder only");
+        const ActFrag ft = split_act<false>(t, amax);
+        gate_blend_f16x3(W, ft.hi, ft.lo, skip, b, lane);   // :156, :164, :169-170
+        return;
+    }
     dense64<BF>(W + BLK_R2_A, W + BLK_R2_B, t, r, lane, amax);  // :156
     dense64<BF>(W + BLK_G_A, W + BLK_G_B, r, t, lane, amax);    // gating logits (+ gate_offset in bias), :164
 #pragma unroll

@@ -106,6 +106,52 @@ __global__ void pack_kernel(EncLayout e, qb::CanonLayout c, float gate_offset, b
     }
 }
 
+// The folded gate ops of the fused inference kernels (vi_kernels.hip, block_stream2<.., FOLD>): per block one dense op
+// in the layout of the image's ops, 4096 floats of A fragments [s][m][part][lane][8] and 64 floats of bias [m][g][r],
+//   A = -log2(e) (Wr2 Wg),   bias = -log2(e) (br2 Wg + bg + gate_offset),
+// so that the gate logits come from relu(t)'s fragments and the sigmoid is rcp(1 + exp2(.)).  One thread per element:
+// the 64-term product in float64, rounded once to float32, then split into f16 halves like every other weight (a folded
+// weight beyond the f16 range goes to the fold buffer's own flag slot, behind the L ops).  Always the split-f16 form:
+// the folded kernels exist for that encoder only (vi_kernels.hip).
+constexpr int kFoldOp = qb::BLK_FLOATS - qb::BLK_G_A;   // 4160 floats
+__global__ void gatefold_pack_kernel(qb::CanonLayout c, float gate_offset, const float* __restrict__ w,
+                                     float* __restrict__ fold) {
+    const int U = c.U, G = c.G;
+    const double nlog2e = -1.4426950408889634;
+    float* flag = fold + c.L * kFoldOp;
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < c.L * kFoldOp; p += gridDim.x * blockDim.x) {
+        const int l = p / kFoldOp, o = p % kFoldOp;
+        const float* wb = w + c.blk0 + l * c.blk_stride;
+        const float* Wr2 = wb + c.Wr2 + (c.taps == 9 ? 4 * U * U : 0);   // centre tap, as pack_kernel
+        const float* Wg = wb + c.Wg;
+        float* op = fold + l * kFoldOp;
+        if (o < 4096) {   // element (s, m, lane, j): both of its halves
+            const int j = o & 7, lane = (o >> 3) & 63, m = (o >> 9) & 3, s = o >> 11;
+            const int in = frag_unit(s, lane >> 4, j), out = 16 * m + (lane & 15);
+            double acc = 0.0;
+            if (in < U && out < U) {
+                const int col = G == 1 ? 0 : out;   // shared gate broadcast to all units
+                for (int k = 0; k < U; ++k) acc = fma((double)Wr2[in * U + k], (double)Wg[k * G + col], acc);
+            }
+            const float v = (float)(nlog2e * acc);
+            _Float16* ph = reinterpret_cast<_Float16*>(op);
+            const int h = j + 8 * lane + 1024 * m + 4096 * s;
+            ph[h] = split_part(v, 0, false, flag);
+            ph[h + 512] = split_part(v, 1, false, flag);
+        } else {
+            const int qq = o - 4096, r = qq & 3, g = (qq >> 2) & 3, m = qq >> 4;
+            const int u = qb::acc_unit(m, r, g);
+            double acc = 0.0;
+            if (u < U) {
+                const int col = G == 1 ? 0 : u;
+                acc = (double)wb[c.bg + col] + (double)gate_offset;
+                for (int k = 0; k < U; ++k) acc = fma((double)wb[c.br2 + k], (double)Wg[k * G + col], acc);
+            }
+            op[o] = (float)(nlog2e * acc);
+        }
+    }
+}
+
 constexpr int kEncBlock = 1024;
 
 template <int T, int NL, bool BF>
@@ -365,6 +411,26 @@ extern "C" int qbold_encoder_pack(const qbold_ctx* ctx, const qbold_encoder_shap
     QB_HIP(hipMemsetAsync(packed + e.flag, 0, sizeof(float), (hipStream_t)stream));
     hipLaunchKernelGGL(pack_kernel, dim3((2 * e.total + 255) / 256), dim3(256), 0, (hipStream_t)stream, e,
                        c, shape->gate_offset, shape->precision == QBOLD_ENC_BF16, weights, packed);
+    QB_HIP(hipGetLastError());
+    return QBOLD_OK;
+}
+
+extern "C" int64_t qbold_encoder_gatefold_floats(const qbold_encoder_shape* s) {
+    if (!s || s->L < 1) return QBOLD_ERR_INVALID;
+    return (int64_t)s->L * kFoldOp + 4;   // L ops, the flag slot, padding to a float4
+}
+
+extern "C" int qbold_encoder_pack_gatefold(const qbold_ctx* ctx, const qbold_encoder_shape* shape,
+                                           const float* weights, float* fold, void* stream) {
+    QB_NEED_DEVICE(ctx);
+    int rc = qb::check_encoder_shape(ctx, shape);
+    if (rc) return rc;
+    QB_REQUIRE(weights && fold, "qbold_encoder_pack_gatefold: null buffer");
+    const qb::CanonLayout c = qb::make_canon(shape->T, shape->U, shape->L, shape->channelwise_gating,
+                                             shape->spatial_taps);
+    QB_HIP(hipMemsetAsync(fold + shape->L * kFoldOp, 0, 4 * sizeof(float), (hipStream_t)stream));
+    hipLaunchKernelGGL(gatefold_pack_kernel, dim3((shape->L * kFoldOp + 255) / 256), dim3(256), 0,
+                       (hipStream_t)stream, c, shape->gate_offset, weights, fold);
     QB_HIP(hipGetLastError());
     return QBOLD_OK;
 }

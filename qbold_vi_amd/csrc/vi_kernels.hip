@@ -35,6 +35,17 @@
 // gather_head has just handed them, one select per row.  qbold_vi_fwd sends whole balanced rounds of 64-voxel tiles
 // (64 voxels on every wave of the device) to vi_fwd_kernel_vox and the remainder to vi_fwd_kernel.
 //
+// The folded gate image (qbold_vi_fwd_folded; ops.vi_fwd's default).  A block's gate logits, Wg r + bg + gate_offset
+// with r = Wr2 relu(t) + br2, are affine in relu(t): (Wr2 Wg) relu(t) + (br2 Wg + bg + gate_offset).  The weights do
+// not change between calls, so qbold_encoder_pack_gatefold forms that product once (float64, one rounding, times
+// -log2(e)) as one more dense op per block, and vi_fwd_kernel_fold / vi_fwd_kernel_vox_fold -- the same text as the two
+// kernels above, vi_fwd_kernels.inc -- stage it in the image's gate slots (same LDS footprint, same single barrier).
+// A block then takes r and the logits from ONE set of fragments: no operand split of r (40 vector instructions per
+// block and sub-tile), no multiply in the sigmoid, a three-instruction blend (32 more), and the gate MFMAs no longer
+// wait for the Wr2 product.  Built for the per-tau-table fast path with the split-f16 encoder, both layouts together;
+// everything else (the bf16 encoder included: there the product's rounding would be bf16's own), and qbold_vi_fwd
+// itself, runs the classic image.  The range guard starts from the larger of the two flag slots.
+//
 // Wide encoders (U = 256, T <= 16 or 49..64: BASELINE config 3) -- two launches: the one-launch encoder of
 // wide_fused_kernels.hip writes q and log sigma into the caller's workspace (qbold_vi_workspace_bytes), the
 // compile-time-T ELBO kernel of elbo_kernels.hip reads them back.
@@ -83,250 +94,16 @@ template <int T, int SE>
 struct ViLds<T, SE, true> { using type = qb::GtLds<T, SE>; };
 constexpr size_t kLdsLimit = 160 * 1024;   // gfx950: LDS per workgroup
 
-// GT: the sampling fast path reads the per-tau OEF-indexed table (GtLds) instead of the x-indexed one (FwdLds);
-// requires FAST and a compile-time spin-echo index.
-// MIR: the protocol mirrors about the spin echo (qbold_ctx::grid_mirrors): mirrored tau pairs are evaluated once and
-// scored as one merged data point (elbo_core.h, prepare_lik); GT implies it.
-template <int T, int NL, int SE, bool FAST, bool LITERAL, bool BF, bool GT = false, bool MIR = false, int BLK = kBlock>
-__global__ __launch_bounds__(BLK) void vi_fwd_kernel(
-    QbDev c, const float4* __restrict__ g_tab, const float* __restrict__ packed,
-    const float* __restrict__ x, const float* __restrict__ mask, const float* __restrict__ prior,
-    int S, int K, uint64_t seed, int64_t voxel0, float* __restrict__ q_out,
-    float2* __restrict__ nll_kl, double* __restrict__ partials, int64_t N) {
-    // compile-time weight-image layout: every LDS offset below folds into an instruction immediate
-    constexpr EncLayout e = qb::make_enc_layout(T, 64, NL);
-    // the sampling phase's table: per-tau OEF-indexed rows (GtLds) on the fast path with a compile-time spin-echo
-    // index, the x-indexed table + literal nodes (FwdLds) otherwise; g_tab points at the matching device table
-    static_assert(!GT || (FAST && SE >= 0 && qb::gtab_segs(T) > 0), "GT needs the fast path with a compile-time spin echo");
-    static_assert(!MIR || (FAST && SE >= 0), "merged mirror pairs: fast path with a compile-time spin echo");
-    constexpr bool kMir = GT || MIR;
-    using Lds = typename ViLds<T, SE, GT>::type;
-    extern __shared__ __align__(16) unsigned char smem[];
-    float* lds_w = reinterpret_cast<float*>(smem);
-    Lds* L = reinterpret_cast<Lds*>(smem + sizeof(float) * e.total);
-    double* red = reinterpret_cast<double*>(smem + sizeof(float) * e.total + sizeof(Lds));
-    constexpr int kWaves = BLK / 64;
-    qb::copy_to_lds<BLK>(lds_w, packed, e.total / 4);
-    if constexpr (qb::IsGtLds<Lds>::value) {
-        qb::gt_lds_fill(L, g_tab, c);
-    } else {
-        qb::fwd_lds_fill(L, g_tab, true);
-        if (threadIdx.x < QB_MAX_T) L->blood_B[threadIdx.x] = c.blood_B[threadIdx.x];
-    }
-    __syncthreads();
-
-    constexpr int HT = (5 + T + 15) / 16;
-    const int lane0 = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float s_nll = 0.0f, s_kl = 0.0f, s_m = 0.0f;
-    const int64_t ntile = (N + 15) / 16;
-    for (int64_t tile = (int64_t)blockIdx.x * kWaves + wave; tile < ntile;
-         tile += (int64_t)gridDim.x * kWaves) {
-        // The lane index is made opaque once per tile: everything derived from it (the encoder's LDS fragment
-        // addresses, the voxel's row pointers) is then recomputed per tile -- a handful of vector instructions --
-        // instead of being hoisted out of the tile loop as 20-70 loop-invariant registers that the sampling phase
-        // (which needs none of them) has to spill and reload around itself.
-        int lane = lane0;
-        asm volatile("" : "+v"(lane));
-        const int g = lane >> 4, i = lane & 15;
-        const int64_t v = tile * 16 + i;
-        const int64_t vc = v < N ? v : N - 1;
-        float o[5 + T];
-        // largest activation this lane split (operand range guard, encoder_core.h); starts from the image's flag
-        // slot: 0, or the largest weight the pack kernel could not split
-        float amax = lds_w[e.flag];
-        {
-            __builtin_amdgcn_s_setprio(QB_PRIO_TILE_START);
-            float xv[T], nv[T];
-#pragma unroll
-            for (int t = 0; t < T; ++t) xv[t] = x[vc * T + t];
-            qb::normalise<T, SE>(c, xv, nv);
-            __builtin_amdgcn_s_setprio(2);
-            f32x4 b[4];
-            qb::dense_first<T, BF>(lds_w + e.first_A, lds_w + e.first_b, nv, b, lane);
-            if (!QB_ABLATE(c, 1) && qb_phase_fence()) {
-                // block 0 reads dense_first's output, which its relu4 left non-negative
-                qb::block_stream2<BF, true>(lds_w + e.blk0, b, lane, &amax);
-#pragma unroll
-                for (int l = 1; l < NL; ++l) qb::block_stream2<BF>(lds_w + e.blk0 + l * e.blk_stride, b, lane, &amax);
-            }
-            f32x4 hd[HT];
-            qb::dense_head<HT, BF>(lds_w + e.head_A, lds_w + e.head_b, b, hd, lane, &amax);
-            qb::gather_head<5 + T, HT>(hd, o);
-            __builtin_amdgcn_s_setprio(0);
-        }
-        if (v < N && !QB_ABLATE(c, 2) && qb_phase_fence()) {
-            // x is read again (an L1/L2 hit) rather than held in 11 VGPRs across the encoder; the
-            // empty asm keeps the compiler from merging the two reads
-            const float* xr = x + v * T;
-            asm volatile("" : "+v"(xr));
-            float xv[T], sv[T], qv[5];
-#pragma unroll
-            for (int t = 0; t < T; ++t) xv[t] = xr[t];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) qv[k] = o[k];
-#pragma unroll
-            for (int t = 0; t < T; ++t) sv[t] = o[5 + t];  // log sigma; sigma = exp(.), model.py:214
-            // the mask: the likelihood needs it only on log data (model.py:548); the sums read it again after the draws
-            // (a second load through an opaque pointer) instead of carrying it through the loops
-            qb::VoxelLik<T> lik;
-            qb::prepare_lik<T, SE, true, (FAST && SE >= 0), FAST, kMir>(c, xv, sv, FAST ? 1.0f : (mask ? mask[v] : 1.0f), lik);
-            const qb::LogitMvn qm = qb::make_mvn(qv);
-            // posterior parameters leave before the draws (lane group 1), so that they do not live through them
-            if (g == 1 && q_out) {
-#pragma unroll
-                for (int k = 0; k < 5; ++k) q_out[v * 5 + k] = qv[k];
-            }
-            // an activation beyond the f16 operand range: this voxel's terms become NaN (never a silent clamp) -- through
-            // the per-draw constant, which every draw's NLL adds
-            if (!BF && qb::split_overflowed(amax)) lik.log_s_sum = __builtin_nanf("");
-            float nll_part, kl_part;
-            qb::voxel_mc_sums<T, SE, FAST, LITERAL, kMir>(L, c, lik, qm, prior + v * 5, S, K, nullptr, nullptr, seed,
-                                                    (uint64_t)(voxel0 + v), g, nll_part, kl_part);
-            const float nll = qb::voxel_sum(nll_part) / (float)S;
-            const float kl = K > 0 ? qb::voxel_sum(kl_part) / (float)K : 0.0f;
-            if (g == 0) {
-                const float* mp = mask;
-                asm volatile("" : "+v"(mp));
-                const float m = mp ? mp[v] : 1.0f;
-                if (nll_kl) nll_kl[v] = make_float2(nll, kl);
-                s_nll += nll * m;              // model.py:564
-                s_kl += m > 0.0f ? kl : 0.0f;  // model.py:661
-                s_m += m;
-            }
-        }
-    }
-    qb::block_partials(red, s_nll, s_kl, s_m, partials);
-}
-
-// The same tile loop with one lane per voxel through the sampling phase (header comment).  Per 64-voxel tile the encoder
-// phase runs four times, on the 16-voxel sub-tiles s = 0 .. 3, exactly as in vi_fwd_kernel; after sub-tile s the lanes
-// of group s keep their gathered head rows (a select per row: gather_head has just handed every group a copy), so that
-// lane (g, i) ends up with the heads of voxel 64 tile + 16 g + i = 64 tile + lane.  The sampling phase then runs once,
-// voxel_mc_sums<.., 1> walking the four draw shares in vi_fwd_kernel's order (elbo_core.h): every per-voxel output is
-// the same bits whichever kernel took the voxel.  Built for the per-tau-table fast path only (GT in vi_fwd_kernel's
-// terms).  add_blocks: workgroups below it add their partial sums to what the slot holds (the four-lane launch over
-// the batch's remainder wrote it earlier on the stream) instead of overwriting it.
-template <int T, int NL, int SE, bool BF, int BLK = kBlock>
-__global__ __launch_bounds__(BLK) void vi_fwd_kernel_vox(
-    QbDev c, const float4* __restrict__ g_tab, const float* __restrict__ packed,
-    const float* __restrict__ x, const float* __restrict__ mask, const float* __restrict__ prior,
-    int S, int K, uint64_t seed, int64_t voxel0, float* __restrict__ q_out,
-    float2* __restrict__ nll_kl, double* __restrict__ partials, int64_t N, int add_blocks) {
-    constexpr EncLayout e = qb::make_enc_layout(T, 64, NL);
-    static_assert(SE >= 0 && qb::gtab_segs(T) > 0, "built for the per-tau table with a compile-time spin echo");
-    using Lds = qb::GtLds<T, SE>;
-    extern __shared__ __align__(16) unsigned char smem[];
-    float* lds_w = reinterpret_cast<float*>(smem);
-    Lds* L = reinterpret_cast<Lds*>(smem + sizeof(float) * e.total);
-    double* red = reinterpret_cast<double*>(smem + sizeof(float) * e.total + sizeof(Lds));
-    constexpr int kWaves = BLK / 64;
-    qb::copy_to_lds<BLK>(lds_w, packed, e.total / 4);
-    qb::gt_lds_fill(L, g_tab, c);
-    __syncthreads();
-
-    constexpr int HT = (5 + T + 15) / 16;
-    // Nothing per lane lives across the tile loop but the thread index: the encoder phases hold the finished sub-tiles'
-    // head rows on top of their own peak, and every further loop-carried vector register would be spilled around them.
-    // The wave index is read as a scalar (the tile counter and its bounds stay on the scalar unit), and the three
-    // running sums are wave-uniform, added up across the wave once per tile.
-    const int lane0 = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float s_nll = 0.0f, s_kl = 0.0f, s_m = 0.0f;
-    auto uniform = [](float v) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v))); };
-    const int64_t ntile = (N + 63) / 64;
-    for (int64_t tile = (int64_t)blockIdx.x * kWaves + wave; tile < ntile;
-         tile += (int64_t)gridDim.x * kWaves) {
-        float o[5 + T];
-#pragma unroll
-        for (int k = 0; k < 5 + T; ++k) o[k] = 0.0f;
-        // operand range guard: bit l = the voxel of lane l had an activation beyond the split's range in any of the four
-        // lane groups that encoded it (a wave-uniform mask: it costs no vector register across the encoder phases)
-        unsigned long long hot = 0;
-#pragma unroll 1
-        for (int s = 0; s < 4; ++s) {
-            // the lane index is made opaque per sub-tile, as vi_fwd_kernel makes it per tile: what derives from it (the
-            // encoder's LDS fragment addresses) is formed again for each sub-tile instead of living through all four
-            int lane = lane0;
-            asm volatile("" : "+v"(lane));
-            const int g = lane >> 4, i = lane & 15;
-            const int64_t ve = tile * 64 + 16 * s + i;
-            const int64_t vc = ve < N ? ve : N - 1;
-            float amax = lds_w[e.flag];
-            __builtin_amdgcn_s_setprio(QB_PRIO_TILE_START);
-            float xv[T], nv[T];
-#pragma unroll
-            for (int t = 0; t < T; ++t) xv[t] = x[vc * T + t];
-            qb::normalise<T, SE>(c, xv, nv);
-            __builtin_amdgcn_s_setprio(2);
-            f32x4 b[4];
-            qb::dense_first<T, BF>(lds_w + e.first_A, lds_w + e.first_b, nv, b, lane);
-            if (!QB_ABLATE(c, 1) && qb_phase_fence()) {
-                qb::block_stream2<BF, true>(lds_w + e.blk0, b, lane, &amax);
-#pragma unroll
-                for (int l = 1; l < NL; ++l) qb::block_stream2<BF>(lds_w + e.blk0 + l * e.blk_stride, b, lane, &amax);
-            }
-            f32x4 hd[HT];
-            qb::dense_head<HT, BF>(lds_w + e.head_A, lds_w + e.head_b, b, hd, lane, &amax);
-            float os[5 + T];
-            qb::gather_head<5 + T, HT>(hd, os);
-#pragma unroll
-            for (int k = 0; k < 5 + T; ++k) o[k] = g == s ? os[k] : o[k];
-            if constexpr (!BF) {
-                unsigned long long over = __ballot(qb::split_overflowed(amax));
-                over |= over >> 32;
-                over |= over >> 16;
-                hot |= (over & 0xffffull) << (16 * s);
-            }
-        }
-        __builtin_amdgcn_s_setprio(0);
-        int lane = lane0;
-        asm volatile("" : "+v"(lane));
-        const int64_t v = tile * 64 + lane;
-        float t_nll = 0.0f, t_kl = 0.0f, t_m = 0.0f;   // this lane's terms of the three masked sums
-        if (v < N && !QB_ABLATE(c, 2) && qb_phase_fence()) {
-            const float* xr = x + v * T;   // read again rather than held across the encoder phases (vi_fwd_kernel)
-            asm volatile("" : "+v"(xr));
-            float xv[T], sv[T], qv[5];
-#pragma unroll
-            for (int t = 0; t < T; ++t) xv[t] = xr[t];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) qv[k] = o[k];
-#pragma unroll
-            for (int t = 0; t < T; ++t) sv[t] = o[5 + t];
-            qb::VoxelLik<T> lik;
-            qb::prepare_lik<T, SE, true, true, true, true>(c, xv, sv, 1.0f, lik);
-            const qb::LogitMvn qm = qb::make_mvn(qv);
-            if (q_out) {
-#pragma unroll
-                for (int k = 0; k < 5; ++k) q_out[v * 5 + k] = qv[k];
-            }
-            if (!BF && ((hot >> lane) & 1)) lik.log_s_sum = __builtin_nanf("");
-            float nll_sum, kl_sum;
-            qb::voxel_mc_sums<T, SE, true, false, true, 1>(L, c, lik, qm, prior + v * 5, S, K, nullptr, nullptr, seed,
-                                                           (uint64_t)(voxel0 + v), 0, nll_sum, kl_sum);
-            int Sd = S, Kd = K;   // opaque: (float)S and (float)K are formed here, not carried through the tile loop
-            asm volatile("" : "+s"(Sd), "+s"(Kd));
-            const float nll = nll_sum / (float)Sd;
-            const float kl = Kd > 0 ? kl_sum / (float)Kd : 0.0f;
-            // the voxel index is formed again for the outputs rather than carried through the draw loops
-            int lane_out = lane0;
-            asm volatile("" : "+v"(lane_out));
-            const int64_t vo = tile * 64 + lane_out;
-            const float* mp = mask;
-            asm volatile("" : "+v"(mp));
-            const float m = mp ? mp[vo] : 1.0f;
-            if (nll_kl) nll_kl[vo] = make_float2(nll, kl);
-            t_nll = nll * m;              // model.py:564
-            t_kl = m > 0.0f ? kl : 0.0f;  // model.py:661
-            t_m = m;
-        }
-        s_nll = uniform(s_nll + qb::wave_sum(t_nll));
-        s_kl = uniform(s_kl + qb::wave_sum(t_kl));
-        s_m = uniform(s_m + qb::wave_sum(t_m));
-    }
-    const bool first = (threadIdx.x & 63) == 0;   // the wave's sums enter the block reduction once
-    qb::block_partials(red, first ? s_nll : 0.0f, first ? s_kl : 0.0f, first ? s_m : 0.0f, partials,
-                       (int)blockIdx.x < add_blocks);
-}
+// The two kernel templates live in vi_fwd_kernels.inc and are compiled from that one text twice: as vi_fwd_kernel /
+// vi_fwd_kernel_vox on the classic image, and as vi_fwd_kernel_fold / vi_fwd_kernel_vox_fold with one more argument,
+// the folded gate ops of qbold_encoder_pack_gatefold (header of the .inc).  Two names rather than a template
+// parameter: the classic kernels keep their symbols and, token for token the same source, their listings.
+#define QB_VI_FOLD 0
+#include "vi_fwd_kernels.inc"
+#undef QB_VI_FOLD
+#define QB_VI_FOLD 1
+#include "vi_fwd_kernels.inc"
+#undef QB_VI_FOLD
 
 }  // namespace
 
@@ -355,11 +132,13 @@ extern "C" int64_t qbold_vi_workspace_bytes(const qbold_ctx* ctx, const qbold_en
     return part + align256(N * (int64_t)shape->T * 4) + align256(N * 5 * 4);
 }
 
-extern "C" int qbold_vi_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* shape,
-                            const float* packed, const float* x, const float* mask,
-                            const float* prior, int S, int K, uint64_t seed, int64_t voxel0,
-                            float* q_out, float* nll_kl, double* sums, void* workspace, int64_t N,
-                            void* stream) {
+namespace {
+// qbold_vi_fwd (gate_fold = NULL) and qbold_vi_fwd_folded.  The folded gate ops are used where the FOLD kernels are
+// built: the per-tau-table fast path of the narrow shapes, on both layouts of the sampling phase together (per-voxel
+// outputs do not depend on which kernel took a voxel); everywhere else gate_fold is ignored.
+int vi_fwd_run(const qbold_ctx* ctx, const qbold_encoder_shape* shape, const float* packed, const float* gate_fold,
+               const float* x, const float* mask, const float* prior, int S, int K, uint64_t seed, int64_t voxel0,
+               float* q_out, float* nll_kl, double* sums, void* workspace, int64_t N, void* stream) {
     QB_NEED_DEVICE(ctx);
     QB_RELU_ONLY(shape, "qbold_vi_fwd");
     if (wide_vi_path(ctx, shape)) {
@@ -401,6 +180,14 @@ extern "C" int qbold_vi_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* sha
     const bool vox_kernel = !(ctx->kernel_sel & QBOLD_KSEL_VI_FOUR_LANE) && vox_kernel_built(shape->T, shape->L) && fast &&
                             qb::gtab_segs(shape->T) > 0 && ctx->dev.se_idx == (shape->T == 24 ? 7 : 2) &&
                             !ctx->dev.multi_norm && !(ctx->kernel_sel & (4 | 8)) && ctx->gtab_ok;
+    // the folded gate ops: wherever the per-tau-table kernels run (the condition of QB_DISPATCH_VI's first branch)
+    // (split-f16 only: rounded to bf16 the product matrix is another arithmetic than qbold_encoder_fwd's bf16 mode,
+    // 1e-3 apart on q -- MEASUREMENTS.md 28 -- so QBOLD_ENC_BF16 keeps the two-step form)
+    const bool fold = gate_fold && !bf && vox_kernel_built(shape->T, shape->L) && fast && qb::gtab_segs(shape->T) > 0 &&
+                      ctx->dev.se_idx == (shape->T == 24 ? 7 : 2) && !ctx->dev.multi_norm &&
+                      !(ctx->kernel_sel & (4 | 8)) && ctx->gtab_ok;
+    QB_REQUIRE(!fold || reinterpret_cast<uintptr_t>(gate_fold) % 16 == 0,
+               "qbold_vi_fwd_folded: gate_fold must be 16-byte aligned");
     const int64_t round = (ctx->kernel_sel & QBOLD_KSEL_VI_WHOLE_TILES) ? 64 : 64 * (int64_t)ctx->num_cus * waves;
     const int64_t n_vox = vox_kernel ? N / round * round : 0;
     // the reduced-precision encoder is built for the table-mode fast path (the bench / training
@@ -422,8 +209,20 @@ extern "C" int qbold_vi_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* sha
         hipLaunchKernelGGL(k, dim3(grid), dim3(BLKT), smem, s, ctx->dev, tab, packed,              \
                            x, mask, prior, S, K, seed, voxel0, q_out, out, partials, N);          \
     } while (0)
+#define QB_LAUNCH_VI_FOLD(TT, NL, SEC)                                                             \
+    do {                                                                                          \
+        constexpr size_t smem = sizeof(float) * qb::make_enc_layout(TT, 64, NL).total +            \
+                                sizeof(qb::GtLds<TT, SEC>) + sizeof(double) * 3 * (kBlock / 64);   \
+        static_assert(smem <= kLdsLimit, "weight image + sampling table exceed the LDS");          \
+        constexpr int BLKT = TT == 24 ? QB_VI_BLOCK_24 : kBlock;                                   \
+        auto k = vi_fwd_kernel_fold<TT, NL, SEC, true, false, false, true, false, BLKT>;           \
+        QB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k),                              \
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));       \
+        hipLaunchKernelGGL(k, dim3(grid), dim3(BLKT), smem, s, ctx->dev, ctx->d_gtab, packed,      \
+                           gate_fold, x, mask, prior, S, K, seed, voxel0, q_out, out, partials, N); \
+    } while (0)
     // SEC: the protocol's spin-echo index (tau = 0), folded at compile time when the context agrees
-#define QB_DISPATCH_VI(TT, NL, SEC)                                               \
+#define QB_DISPATCH_VI(TT, NL, SEC)                                              \
     do {                                                                          \
         if (qb::gtab_segs(TT) > 0 && fast && ctx->dev.se_idx == SEC && !ctx->dev.multi_norm && !(ctx->kernel_sel & 4) && ctx->gtab_ok && !(ctx->kernel_sel & 8)) QB_LAUNCH_VI_GT(TT, NL, SEC, true, false, (qb::gtab_segs(TT) > 0), false);   \
         else if (fast && ctx->dev.se_idx == SEC && !ctx->dev.multi_norm && !(ctx->kernel_sel & 4) && ctx->grid_mirrors) QB_LAUNCH_VI_GT(TT, NL, SEC, true, false, false, true);   \
@@ -439,7 +238,17 @@ extern "C" int qbold_vi_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* sha
         const int64_t ntile = (N + 15) / 16;
         const int64_t nblk = (ntile + waves - 1) / waves;
         grid = (int)(nblk < ctx->num_cus ? (nblk > 0 ? nblk : 1) : ctx->num_cus);
-#ifdef QB_VI_PROBE   // scripts/dev/resources.sh: compile the optimal.yaml depth only (register / scratch reports in seconds)
+        if (fold) {
+            if (shape->T == 11 && shape->L == 2) QB_LAUNCH_VI_FOLD(11, 2, 2);
+#ifndef QB_VI_PROBE
+            else if (shape->T == 11 && shape->L == 1) QB_LAUNCH_VI_FOLD(11, 1, 2);
+            else if (shape->T == 24 && shape->L == 1) QB_LAUNCH_VI_FOLD(24, 1, 7);
+#endif
+            else QB_LAUNCH_VI_FOLD(24, 2, 7);
+            QB_HIP(hipGetLastError());
+            return QBOLD_OK;
+        }
+#ifdef QB_VI_PROBE  // scripts/dev/resources.sh: compile the optimal.yaml depth only (register / scratch reports in seconds)
         if (shape->T == 11 && shape->L == 2) QB_DISPATCH_VI(11, 2, 2);
         else if (shape->T == 24 && shape->L == 2) QB_DISPATCH_VI(24, 2, 7);
 #else
@@ -467,6 +276,18 @@ extern "C" int qbold_vi_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* sha
         hipLaunchKernelGGL(k, dim3(vgrid), dim3(BLKT), smem, s, ctx->dev, ctx->d_gtab, packed, x, mask, \
                            prior, S, K, seed, voxel0, q_out, out, partials, n_vox, grid);             \
     } while (0)
+#define QB_LAUNCH_VOX_FOLD(TT, NL, SEC)                                                                \
+    do {                                                                                              \
+        constexpr size_t smem = sizeof(float) * qb::make_enc_layout(TT, 64, NL).total +                \
+                                sizeof(qb::GtLds<TT, SEC>) + sizeof(double) * 3 * (kBlock / 64);       \
+        static_assert(smem <= kLdsLimit, "weight image + sampling table exceed the LDS");              \
+        constexpr int BLKT = TT == 24 ? QB_VI_BLOCK_24 : kBlock;                                       \
+        auto k = vi_fwd_kernel_vox_fold<TT, NL, SEC, false, BLKT>;                                     \
+        QB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                  \
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));           \
+        hipLaunchKernelGGL(k, dim3(vgrid), dim3(BLKT), smem, s, ctx->dev, ctx->d_gtab, packed, gate_fold, x, mask, \
+                           prior, S, K, seed, voxel0, q_out, out, partials, n_vox, grid);             \
+    } while (0)
     float2* out = reinterpret_cast<float2*>(nll_kl);
     int grid = 0;   // partial-sum slots holding a value
     if (n_vox < N || N == 0) {
@@ -479,7 +300,15 @@ extern "C" int qbold_vi_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* sha
         // per slot, in stream order: deterministic), so the workspace holds one slot per workgroup as before
         const int64_t nblk = (n_vox / 64 + waves - 1) / waves;
         const int vgrid = (int)(nblk < ctx->num_cus ? nblk : ctx->num_cus);
-        if (shape->T == 11 && shape->L == 2) QB_LAUNCH_VOX(11, 2, 2);
+        if (fold) {
+            if (shape->T == 11 && shape->L == 2) QB_LAUNCH_VOX_FOLD(11, 2, 2);
+#ifndef QB_VI_PROBE
+            else if (shape->T == 11 && shape->L == 1) QB_LAUNCH_VOX_FOLD(11, 1, 2);
+            else if (shape->T == 24 && shape->L == 1) QB_LAUNCH_VOX_FOLD(24, 1, 7);
+#endif
+            else QB_LAUNCH_VOX_FOLD(24, 2, 7);
+        }
+        else if (shape->T == 11 && shape->L == 2) QB_LAUNCH_VOX(11, 2, 2);
 #ifndef QB_VI_PROBE
         else if (shape->T == 11 && shape->L == 1) QB_LAUNCH_VOX(11, 1, 2);
         else if (shape->T == 24 && shape->L == 1) QB_LAUNCH_VOX(24, 1, 7);
@@ -489,10 +318,32 @@ extern "C" int qbold_vi_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* sha
         grid = vgrid > grid ? vgrid : grid;
     }
 #undef QB_LAUNCH_VOX
+#undef QB_LAUNCH_VOX_FOLD
+#undef QB_LAUNCH_VI_FOLD
 #undef QB_DISPATCH_VI
 #undef QB_LAUNCH_VI
 #undef QB_LAUNCH_VI_GT
     hipLaunchKernelGGL(qb::reduce_partials_kernel, dim3(1), dim3(192), 0, s, partials, grid, sums);
     QB_HIP(hipGetLastError());
     return QBOLD_OK;
+}
+}  // namespace
+
+extern "C" int qbold_vi_fwd(const qbold_ctx* ctx, const qbold_encoder_shape* shape,
+                            const float* packed, const float* x, const float* mask,
+                            const float* prior, int S, int K, uint64_t seed, int64_t voxel0,
+                            float* q_out, float* nll_kl, double* sums, void* workspace, int64_t N,
+                            void* stream) {
+    return vi_fwd_run(ctx, shape, packed, nullptr, x, mask, prior, S, K, seed, voxel0, q_out, nll_kl, sums, workspace,
+                      N, stream);
+}
+
+extern "C" int qbold_vi_fwd_folded(const qbold_ctx* ctx, const qbold_encoder_shape* shape,
+                                   const float* packed, const float* gate_fold, const float* x, const float* mask,
+                                   const float* prior, int S, int K, uint64_t seed, int64_t voxel0,
+                                   float* q_out, float* nll_kl, double* sums, void* workspace, int64_t N,
+                                   void* stream) {
+    QB_REQUIRE(gate_fold, "qbold_vi_fwd_folded: null gate_fold (qbold_encoder_pack_gatefold fills it)");
+    return vi_fwd_run(ctx, shape, packed, gate_fold, x, mask, prior, S, K, seed, voxel0, q_out, nll_kl, sums,
+                      workspace, N, stream);
 }

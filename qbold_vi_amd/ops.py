@@ -117,7 +117,11 @@ class EncoderWeights:
         self.flat = torch.zeros(self.num_params, dtype=torch.float32, device=ctx.device)
         self.packed = torch.zeros(int(lib.qbold_encoder_packed_floats(C.byref(self.shape))),
                                   dtype=torch.float32, device=ctx.device)
-        self._dirty = {"packed", "wide", "fused"}   # device images to rebuild from the canonical blob
+        self._dirty = {"packed", "wide", "fused", "fold"}   # device images to rebuild from the canonical blob
+        # folded gate ops of the fused ELBO kernels (qbold_vi_fwd_folded): -log2(e) (Wr2 Wg) per block, built lazily
+        self.gate_fold = (torch.zeros(int(lib.qbold_encoder_gatefold_floats(C.byref(self.shape))),
+                                      dtype=torch.float32, device=ctx.device)
+                          if Context.fits_fused(self.shape) else None)
         # weight-streaming image for widths beyond the LDS-resident kernels (U = 128 / 256)
         n_wide = int(lib.qbold_encoder_wide_packed_floats(C.byref(self.shape)))
         # gelu runs on the general layer-wise kernels only (include/qbold_hip.h, qbold_activation)
@@ -183,7 +187,7 @@ class EncoderWeights:
         return out
 
     def mark_dirty(self):
-        self._dirty = {"packed", "wide", "fused"}
+        self._dirty = {"packed", "wide", "fused", "fold"}
 
     # the tensors stream 1 (the pre-training output, model.py:199) depends on; every other variable gets a None
     # gradient from Keras' loss=[synthetic_data_loss, None, None] (train.py:388-392) and is left alone by
@@ -225,6 +229,14 @@ class EncoderWeights:
             self._wide_ws = torch.empty(n, dtype=torch.float32, device=self.flat.device)
             self._wide_ws_n = N
         return self._wide_ws
+
+    def gate_fold_ptr(self):
+        if "fold" in self._dirty:
+            _lib.check(_lib.load().qbold_encoder_pack_gatefold(self.ctx.handle, C.byref(self.shape),
+                                                               _ptr(self.flat), _ptr(self.gate_fold), _stream()),
+                       "qbold_encoder_pack_gatefold")
+            self._dirty.discard("fold")
+        return _ptr(self.gate_fold)
 
     def packed_ptr(self):
         if "packed" in self._dirty:
@@ -860,8 +872,14 @@ class Context:
         return sums, q2, nk
 
     def vi_fwd(self, weights, x, mask, prior, S=1, K=70, seed=1, voxel0=0, want_q=True,
-               per_voxel=True, out=None, range_check=False):
+               per_voxel=True, out=None, range_check=False, fold_gate=True):
         """Fused encoder + ELBO.  Returns (sums, q [N,5] or None, nll_kl [N,2] or None).
+
+        fold_gate: the narrow fused kernels take each block's gate logits from relu(t) through the product matrix
+        Wr2 Wg, packed once per weight update (qbold_vi_fwd_folded); False keeps the two-step form of qbold_vi_fwd
+        (the comparator: same results to float32 rounding of the product, not the same bits).  The folded kernels
+        exist for the float32-grade encoder on the per-tau-table fast path; elsewhere (precision='bf16', off-grid
+        protocols, literal tissue mode) the folded entry runs the two-step kernels.
 
         range_check: the MFMA encoders split every operand into two f16 halves (float32-grade for
         6.1e-5 <= |x| <= 65504, include/qbold_hip.h); an activation beyond 65504 overflows to inf and surfaces as
@@ -874,7 +892,8 @@ class Context:
         prior = _f32(prior, "prior", 5)
         mask = _f32(mask, "mask") if mask is not None else None
         if range_check:
-            sums, qo, nk = self.vi_fwd(weights, x, mask, prior, S, K, seed, voxel0, want_q, per_voxel, out)
+            sums, qo, nk = self.vi_fwd(weights, x, mask, prior, S, K, seed, voxel0, want_q, per_voxel, out,
+                                       fold_gate=fold_gate)
             if N > 0 and not bool(torch.isfinite(sums).all()):
                 sums2, q2, nk2 = self.vi_fwd_exact(weights, x, mask, prior, S, K, seed, voxel0)
                 if bool(torch.isfinite(sums2).all()):   # the split overflowed, float32 did not
@@ -915,6 +934,12 @@ class Context:
             nk = torch.empty((N, 2), dtype=torch.float32, device=x.device) if per_voxel else None
         else:
             sums, qo, nk = out
+        if fold_gate:
+            _lib.check(self.lib.qbold_vi_fwd_folded(self.handle, C.byref(weights.shape), weights.packed_ptr(),
+                                                    weights.gate_fold_ptr(), _ptr(x), _ptr(mask), _ptr(prior), int(S),
+                                                    int(K), int(seed), int(voxel0), _ptr(qo), _ptr(nk), _ptr(sums),
+                                                    _ptr(self._workspace()), N, _stream()), "qbold_vi_fwd_folded")
+            return sums, qo, nk
         _lib.check(self.lib.qbold_vi_fwd(self.handle, C.byref(weights.shape), weights.packed_ptr(),
                                          _ptr(x), _ptr(mask), _ptr(prior), int(S), int(K), int(seed),
                                          int(voxel0), _ptr(qo), _ptr(nk), _ptr(sums),
