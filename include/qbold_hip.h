@@ -534,6 +534,29 @@ int qbold_refine_posterior_spatial(const qbold_ctx* ctx, const float* x, const f
                                    const qbold_refine_cfg* cfg, uint64_t seed, int64_t voxel0,
                                    float* q_out, float* loss, void* workspace, void* stream);
 
+/* The two refinements on any tau grid, 1 <= T <= 64 (run-time-T kernels: the voxel's normalised data and 1 / sigma in
+ * LDS, heads and optimiser state in registers).  Arguments, draws (Philox stream 7 or z), schedule, optimisers, loss,
+ * masked voxels, aliasing, the 88-byte-per-voxel workspace (qbold_refine_spatial_workspace_bytes) and the
+ * QBOLD_ERR_INVALID cases are those of qbold_refine_posterior / qbold_refine_posterior_spatial, which are unchanged:
+ * they keep their T = 11 / 24 kernels, their bits, and QBOLD_ERR_UNSUPPORTED for every other T.
+ *   These entries take T = 11 and 24 too and run the run-time-T kernels there: the same function on the same draws,
+ *   the gradient sums regrouped (one pass over the taus per draw), so they agree with the specialised kernels to
+ *   rounding, not to the bit.  qbold_refine_posterior_spatial_anyt with tv_weight = 0 runs
+ *   qbold_refine_posterior_anyt itself (its bits).
+ *   Traffic per voxel: per-voxel entry 4 (2 T + 10 + 1) B in and 20 (+ 8 with loss) B out whatever the number of
+ *   steps (+ 8 Sp B of z per step when given); spatial entry, per step, 4 (2 T + 21) B in and 68 B out, as
+ *   qbold_refine_posterior_spatial.
+ * QBOLD_ERR_UNSUPPORTED only for the literal tissue mode or a context without the full signal model. */
+int qbold_refine_posterior_anyt(const qbold_ctx* ctx, const float* x, const float* mask, const float* q_in,
+                                const float* prior, const float* sigma, const float* z, int steps, int S,
+                                const qbold_refine_cfg* cfg, uint64_t seed, int64_t voxel0,
+                                float* q_out, float* loss, int64_t N, void* stream);
+int qbold_refine_posterior_spatial_anyt(const qbold_ctx* ctx, const float* x, const float* mask, const float* q_in,
+                                        const float* prior, const float* sigma, const float* z,
+                                        const qbold_geometry* geom, float tv_weight, int steps, int S,
+                                        const qbold_refine_cfg* cfg, uint64_t seed, int64_t voxel0,
+                                        float* q_out, float* loss, void* workspace, void* stream);
+
 /* Exact per-voxel posteriors of the fine-tuning model by quadrature on the logit plane (this package's addition; the
  * reference has no counterpart).  With sigma fixed the latent space is u = (a, b), the logits of (OEF, DBV), and
  *   J(u) = -nll(x | OEF(clip a), DBV(clip b); sigma) + log N(u; mu_p, Sigma_p)

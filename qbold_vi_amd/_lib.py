@@ -157,6 +157,11 @@ SIGNATURES = {
     "qbold_refine_spatial_workspace_bytes": (C.c_int64, [_P, C.POINTER(Geometry)]),
     "qbold_refine_posterior_spatial": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(Geometry), C.c_float, C.c_int,
                                                  C.c_int, C.POINTER(RefineCfg), _U64, _I64, _P, _P, _P, _P]),
+    "qbold_refine_posterior_anyt": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(RefineCfg),
+                                              _U64, _I64, _P, _P, _I64, _P]),
+    "qbold_refine_posterior_spatial_anyt": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(Geometry), C.c_float,
+                                                      C.c_int, C.c_int, C.POINTER(RefineCfg), _U64, _I64, _P, _P, _P,
+                                                      _P]),
     "qbold_vi_fwd": (C.c_int, [_P, C.POINTER(EncoderShape), _P, _P, _P, _P, C.c_int, C.c_int,
                                _U64, _I64, _P, _P, _P, _P, _I64, _P]),
     "qbold_encoder_gatefold_floats": (_I64, [C.POINTER(EncoderShape)]),

@@ -376,9 +376,10 @@ class FineTuner:
         return dict(out=out.reshape(lead + (6,)), khat=None if khat is None else khat.reshape(lead), summary=summary)
 
     def refine(self, data, mask, prior, steps=200, no_samples=1, lr=0.1, lr_final=None, optimizer="adam",
-               seed=1, voxel0=0, smoothness_weight=0.0):
+               seed=1, voxel0=0, smoothness_weight=0.0, q=None):
         """Semi-amortised inference (Kim et al. 2018; Cremer et al. 2018): start from the encoder heads of
-        encoder_model.predict (as log_evidence() takes them) and run `steps` Adam / SGD steps on each voxel's own
+        encoder_model.predict (as log_evidence() takes them; or from given heads q [..., 5], laplace()'s say: the best
+        Gaussian under the ELBO from the Laplace fit) and run `steps` Adam / SGD steps on each voxel's own
         E_q[nll] + KL(q || prior), `no_samples` likelihood draws per step, sigma held fixed (the encoder's sigma head
         or the fine tuner's homoscedastic sigma), no TV term (Context.refine_posterior; lr_final None = lr / 10).
         Voxels outside the mask keep the encoder's heads.  Returns dict(q = refined raw heads shaped like the data's
@@ -386,7 +387,9 @@ class FineTuner:
         steps)); q goes unchanged to calculate_means, elbo(q=...), log_evidence(q=...).
         smoothness_weight > 0 (image data [B, X, Y, Z, T] only): refine the volume under the fine-tuning loss's TV
         prior as well, full-batch steps on sum(E_q[nll] + KL) + smoothness_weight TV (Context.refine_posterior_spatial;
-        the configuration's smoothness_weight gives the reference's weighting); 0 is the per-voxel refinement."""
+        the configuration's smoothness_weight gives the reference's weighting); 0 is the per-voxel refinement.
+        Any tau grid of 1 to 64 points: the reference's 11 / 24 taus take the kernels specialised for them, every other
+        grid the run-time-T kernels (Context.refine_posterior's kernel="auto")."""
         tr = self._trainer
         self._check_mvn_family("refine")
         T = data.shape[-1]
@@ -397,7 +400,7 @@ class FineTuner:
         x = _flat(data, T)
         m = None if mask is None else mask.reshape(-1)
         p5 = _flat(prior, prior.shape[-1]).contiguous()
-        q, sg = self._heads_and_sigma(data)
+        q, sg = self._heads_and_sigma(data, q)
         lead = data.shape[:-1]
         if smoothness_weight != 0.0:
             q_out, loss = tr._ctx.refine_posterior_spatial(

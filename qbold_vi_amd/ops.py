@@ -615,16 +615,27 @@ class Context:
                                               int(seed), int(voxel0), _ptr(out), N, _stream()), "qbold_calibration")
         return out
 
+    def _refine_entry(self, what, kernel, name):
+        """The C entry a refinement runs: the specialised kernels' at the reference's 11 / 24 taus (their bits are
+        pinned), the run-time-T kernels' on every other grid or when kernel = "generic"."""
+        if kernel not in ("auto", "generic"):
+            raise ValueError(f"{what}: kernel must be 'auto' or 'generic'")
+        return name if kernel == "auto" and self.T in (11, 24) else name + "_anyt"
+
     def refine_posterior(self, x, mask, q, prior, sigma, steps=200, S=1, lr=0.1, lr_final=None, optimizer="adam",
-                         betas=(0.9, 0.999), eps=1e-8, z=None, seed=1, voxel0=0, want_loss=False):
+                         betas=(0.9, 0.999), eps=1e-8, z=None, seed=1, voxel0=0, want_loss=False, kernel="auto"):
         """Semi-amortised refinement of each voxel's heads (qbold_refine_posterior): `steps` Adam or SGD steps on the
         voxel's E_q[nll] + closed-form KL(q || prior), S likelihood draws per step (Philox stream 7 unless z
         [N, steps, 4 ceil(S / 4), 2] is given), sigma fixed, the rate on a cosine from lr to lr_final (None: lr / 10;
         lr_final = lr is a constant rate).  Voxels with mask <= 0 come back unchanged.
         Defaults: MEASUREMENTS.md section 10.
+        kernel: "auto" runs the kernels specialised for the reference's 11 / 24 taus there and the run-time-T kernel
+        (qbold_refine_posterior_anyt, 1 <= T <= 64) on every other grid; "generic" runs the run-time-T kernel at any T
+        (at 11 / 24 taus it agrees with the specialised kernels to rounding, not to the bit).
         Returns q_out [N, 5] (raw heads, like q) and, with want_loss, loss [N, 2] = (-ELBO estimate at step 0, its
         mean over the last ceil(steps / 10) steps)."""
         steps, S, Sp, cfg = _refine_cfg("refine_posterior", steps, S, lr, lr_final, optimizer, betas, eps)
+        entry = self._refine_entry("refine_posterior", kernel, "qbold_refine_posterior")
         x = _f32(x, "x", self.T)
         N = x.numel() // self.T
         q = _f32(q, "q", 5)
@@ -636,23 +647,24 @@ class Context:
             raise ValueError("z must be [N, steps, 4 ceil(S / 4), 2]")
         q_out = torch.empty((N, 5), dtype=torch.float32, device=x.device)
         loss = torch.empty((N, 2), dtype=torch.float32, device=x.device) if want_loss else None
-        _lib.check(self.lib.qbold_refine_posterior(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior),
-                                                   _ptr(sigma), _ptr(z), steps, S, C.byref(cfg), int(seed),
-                                                   int(voxel0), _ptr(q_out), _ptr(loss), N, _stream()),
-                   "qbold_refine_posterior")
+        _lib.check(getattr(self.lib, entry)(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior), _ptr(sigma),
+                                            _ptr(z), steps, S, C.byref(cfg), int(seed), int(voxel0), _ptr(q_out),
+                                            _ptr(loss), N, _stream()), entry)
         return (q_out, loss) if want_loss else q_out
 
     def refine_posterior_spatial(self, x5, mask5, q5, prior5, sigma5, tv_weight, steps=200, S=1, lr=0.1,
                                  lr_final=None, optimizer="adam", betas=(0.9, 0.999), eps=1e-8, z=None, seed=1,
-                                 voxel0=0, want_loss=False):
+                                 voxel0=0, want_loss=False, kernel="auto"):
         """refine_posterior on a volume under the TV smoothness prior (qbold_refine_posterior_spatial): full-batch Adam
         or SGD on sum over the mask of (E_q[nll] + KL(q || prior)) + tv_weight TV(q), TV = smoothness()'s sum over x-
         and y-neighbour pairs inside the mask (tv_weight = the reference's smoothness_weight gives its fine-tuning
         loss's relative weighting).  x5, sigma5 [B, X, Y, Z, T], q5, prior5 [B, X, Y, Z, 5], mask5 [B, X, Y, Z(, 1)] or
         None (every voxel); z [B X Y Z, steps, 4 ceil(S / 4), 2] or None (Philox stream 7 keyed by voxel0 + the voxel's
         index in the volume).  tv_weight = 0 is refine_posterior on the flattened volume, bit for bit.
+        kernel: as refine_posterior's ("generic": qbold_refine_posterior_spatial_anyt at any T).
         Returns q_out [B, X, Y, Z, 5] and, with want_loss, loss [B, X, Y, Z, 2] (the -ELBO part, as refine_posterior's)."""
         steps, S, Sp, cfg = _refine_cfg("refine_posterior_spatial", steps, S, lr, lr_final, optimizer, betas, eps)
+        entry = self._refine_entry("refine_posterior_spatial", kernel, "qbold_refine_posterior_spatial")
         tv_weight = float(tv_weight)
         if not (math.isfinite(tv_weight) and tv_weight >= 0.0):
             raise ValueError("refine_posterior_spatial: tv_weight must be finite and >= 0")
@@ -680,11 +692,9 @@ class Context:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         q_out = torch.empty(lead + (5,), dtype=torch.float32, device=x.device)
         loss = torch.empty(lead + (2,), dtype=torch.float32, device=x.device) if want_loss else None
-        _lib.check(self.lib.qbold_refine_posterior_spatial(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior),
-                                                           _ptr(sigma), _ptr(z), C.byref(geom), tv_weight, steps, S,
-                                                           C.byref(cfg), int(seed), int(voxel0), _ptr(q_out),
-                                                           _ptr(loss), _ptr(ws), _stream()),
-                   "qbold_refine_posterior_spatial")
+        _lib.check(getattr(self.lib, entry)(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior), _ptr(sigma),
+                                            _ptr(z), C.byref(geom), tv_weight, steps, S, C.byref(cfg), int(seed),
+                                            int(voxel0), _ptr(q_out), _ptr(loss), _ptr(ws), _stream()), entry)
         return (q_out, loss) if want_loss else q_out
 
     GRID_COLUMNS = ("log_p", "elbo_q", "oef", "dbv", "r2p", "oef_sd", "dbv_sd", "r2p_sd", "corr", "oef_lo", "oef_hi",

@@ -246,6 +246,41 @@ def main():
         calls.update(laplace_rows("24", dict(params, tau_start="-0.028", tau_end="0.065", tau_step="0.004")))
         calls.update(laplace_rows("33", dict(params, tau_start="-0.008", tau_end="0.057", tau_step="0.002")))
         calls.update(laplace_rows("64", dict(params, tau_start="-0.008", tau_end="0.0555", tau_step="0.001")))
+    # refinement on any tau grid (the run-time-T kernels): 33 and 64 taus (the Laplace rows' protocols) as the T = 24
+    # rows above have it -- the T = 11 encoder's heads, sigma = 0.05 -- beside the composed loop on the same protocol,
+    # and kernel="generic" at 11 / 24 taus beside the specialised kernels' rows above
+    def refine_anyt_rows(name, p):
+        c = Context(p, True, True)
+        xs = c.signal_fwd(y)
+        sgs = torch.full((n, c.T), 0.05, device="cuda")
+        lss = torch.log(sgs)
+        return {
+            f"refine_posterior(T={name},steps=200,S=1)": (lambda: c.refine_posterior(xs, mask, q, o1, sgs, 200, 1),
+                                                          rbytes(c.T)),
+            f"refine_posterior(T={name},steps=100,S=4)": (lambda: c.refine_posterior(xs, mask, q, o1, sgs, 100, 4),
+                                                          rbytes(c.T)),
+            f"composed_loop(T={name},steps=200,S=1,K=70)": (lambda: composed(c, xs, lss, 200, 1), 0),
+            f"refine_posterior_spatial(T={name},steps=200,S=1,w=5,16x128x64x8)": (
+                lambda: c.refine_posterior_spatial(xs.reshape(16, 128, 64, 8, c.T), vol1m[1], vol1m[2], vol1m[3],
+                                                   sgs.reshape(16, 128, 64, 8, c.T), 5.0, steps=200, S=1),
+                200 * sbytes(c.T)),
+        }
+    if not only_names() or any("T=33" in o or "T=64" in o or "generic" in o for o in only_names()):
+        calls.update(refine_anyt_rows("33", dict(params, tau_start="-0.008", tau_end="0.057", tau_step="0.002")))
+        calls.update(refine_anyt_rows("64", dict(params, tau_start="-0.008", tau_end="0.0555", tau_step="0.001")))
+        calls.update({
+            "refine_posterior(T=11,steps=200,S=1,generic)": (
+                lambda: ctx.refine_posterior(x, mask, q, o1, sg, 200, 1, kernel="generic"), rbytes(T)),
+            "refine_posterior(T=11,steps=100,S=4,generic)": (
+                lambda: ctx.refine_posterior(x, mask, q, o1, sg, 100, 4, kernel="generic"), rbytes(T)),
+            "refine_posterior(T=24,steps=200,S=1,generic)": (
+                lambda: ctx24.refine_posterior(x24, mask, q, o1, sg24, 200, 1, kernel="generic"), rbytes(24)),
+            "refine_posterior(T=24,steps=100,S=4,generic)": (
+                lambda: ctx24.refine_posterior(x24, mask, q, o1, sg24, 100, 4, kernel="generic"), rbytes(24)),
+            "refine_posterior_spatial(T=11,steps=200,S=1,w=5,16x128x64x8,generic)": (
+                lambda: ctx.refine_posterior_spatial(*vol1m[:5], 5.0, steps=200, S=1, kernel="generic"),
+                200 * sbytes(T)),
+        })
     only = only_names()
     out = {}
     for name, (fn, bpv) in calls.items():
