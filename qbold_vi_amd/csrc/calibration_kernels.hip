@@ -19,7 +19,6 @@
 
 namespace {
 
-constexpr uint32_t kStreamIw = 6u;   // the stream of qbold_log_evidence_draws: draw k here is draw k there
 constexpr int kBlock = 256;                                  // 4 waves
 constexpr int kVoxPerBlock = kBlock / QB_LANES_PER_VOXEL;    // 16 voxels per wave, 4 lanes each
 
@@ -162,7 +161,7 @@ __global__ __launch_bounds__(kBlock) void calibration_kernel(
             float zq[8], l[4];
             qb::DrawQuad dq;
             if constexpr (EXPLICIT) cal_load_z(zv, g, cnt, zvec, zq);
-            else dq.load(seed, vox, (uint32_t)g, kStreamIw);
+            else dq.load(seed, vox, (uint32_t)g, qb::STREAM_IW);
             if constexpr (WEIGHTED) cal_load_lw(lwv, g, L, wvec, l);
 #pragma unroll
             for (int d = 0; d < 4; ++d) {

@@ -13,6 +13,7 @@
 // Same lane mapping and Philox stream as the forward kernels, so loss values are identical.
 #include "elbo_core.h"
 #include "qbold_ctx.h"
+#include "signal_grad.h"
 #ifndef QB_BWD_WHITENED
 #define QB_BWD_WHITENED 1
 #endif
@@ -25,37 +26,6 @@ int elbo_grid(const qbold_ctx* ctx);
 namespace {
 
 constexpr int kBlock = 256;
-
-struct FwdGrad {
-    float s, ds_doef, ds_ddbv;
-};
-
-// signal and its partials at tau index t (full model, table mode)
-__device__ __forceinline__ FwdGrad fwd_signal_grad(const qb::FwdLds* L, const QbDev& c,
-                                                   const qb::FwdFast& v, float oef, float dbv, int t) {
-    const float us = fmaf((float)t, v.ub, v.ua);  // signed table coordinate
-    const float u = fabsf(us);
-    const int i = min((int)u, QB_TAB_SEG - 1);
-    const float f = u - (float)i;
-    const float4 k = L->tab[i];
-    const float F = fmaf(fmaf(fmaf(k.w, f, k.z), f, k.y), f, k.x);
-    // dF/dx at |x| (x = u / tab_inv_h), plus node 0's slope; d|x|/doef = |x| / oef
-    const float ax = u * (1.0f / c.tab_inv_h);
-    const float dF = fmaf(fmaf(3.0f * k.w, f, 2.0f * k.z), f, k.y) * c.tab_inv_h + c.dF_node0 * ax;
-    const float e1 = qb::exp2f_(v.nd * F);
-    const float e2 = qb::exp2f_(v.ng * c.blood_B[t]);
-    const float tissue = v.tissue_w * e1, blood = v.blood_w * e2;
-    FwdGrad g;
-    g.s = tissue + blood;
-    const float inv_oef = qb::rcpf_(oef);
-    // tissue: exp(-dbv F(x)), x proportional to oef;  blood: exp(-g B), g proportional to oef^2
-    g.ds_doef = -dbv * dF * ax * inv_oef * tissue +
-                (2.0f * QB_LN2) * v.ng * c.blood_B[t] * inv_oef * blood;
-    // weights: tissue_w = (1 - bw) C1, blood_w = bw C2, bw = m_bld_nb dbv (or dbv without blood)
-    const float dbw = c.include_blood ? c.m_bld_nb : 1.0f;
-    g.ds_ddbv = -F * tissue - dbw * c.e_te_r2t * e1 + (c.include_blood ? dbw * c.e_r2b_te * e2 : 0.0f);
-    return g;
-}
 
 // LPV = lanes per voxel.  4 is the forward kernels' mapping (a voxel's draws dealt to four lanes, lane groups 16
 // apart): right for the evaluation's S = 32 draws.  Training runs the reference's defaults S = 1, K = 70: with four
@@ -177,7 +147,7 @@ __global__ __launch_bounds__(kBlock) void elbo_bwd_kernel(
                         } else if (t == c.se_idx) {
                             gs -= a1;
                         }
-                        const FwdGrad fg = fwd_signal_grad(&L, c, fv, oef, dbv, t);
+                        const qb::FwdGrad fg = qb::fwd_signal_grad(&L, c, fv, oef, dbv, t);
                         g_oef = fmaf(gs, fg.ds_doef, g_oef);
                         g_dbv = fmaf(gs, fg.ds_ddbv, g_dbv);
                     }
@@ -355,7 +325,9 @@ struct GenSig {
     float s, F, e1, e2, u, f, B;
     float4 k;
 };
-// fwd_signal_fast, keeping what the slopes need; blood_B from LDS (t is a run-time index here)
+// fwd_signal_fast, keeping what the slopes need; blood_B from LDS (t is a run-time index here).  This kernel's own
+// evaluation, not signal_grad.h's sig_eval, from which it differs in two ways that its bits rest on: the segment index
+// is not clamped, and s is formed by one fmaf instead of tissue + blood.
 __device__ __forceinline__ GenSig gen_signal(const qb::FwdLds* L, const qb::FwdFast& v, int t) {
     GenSig g;
     g.u = fabsf(fmaf((float)t, v.ub, v.ua));

@@ -1060,7 +1060,7 @@ extern "C" int qbold_kl_diag(const qbold_ctx* ctx, const float* q, const float* 
 // kl_loss against a mixture-of-Gaussians population prior (use_mvg = False, mog_components = M > 1; model.py:666-685):
 // one reparameterised draw per dimension, minus the entropy of q, plus the MEAN of the components' Gaussian NLLs.
 // comps: device [M][4] raw parameters; z: explicit normals [N][2] (OEF, DBV) or NULL for the Philox stream
-// (stream 4, one pair per voxel).
+// (STREAM_KL_MOG, one pair per voxel).
 constexpr int kMaxMog = 16;
 __global__ __launch_bounds__(256) void kl_mog_kernel(const float* __restrict__ q, const float* __restrict__ comps, int M,
                                                      const float* __restrict__ z, uint64_t seed, int64_t voxel0,
@@ -1084,7 +1084,7 @@ __global__ __launch_bounds__(256) void kl_mog_kernel(const float* __restrict__ q
             z1 = z[2 * v + 1];
         } else {
             float zz[4];
-            qb::normals4(seed, (uint64_t)(voxel0 + v), 0u, 4u, zz);
+            qb::normals4(seed, (uint64_t)(voxel0 + v), 0u, qb::STREAM_KL_MOG, zz);
             z0 = zz[0];
             z1 = zz[1];
         }

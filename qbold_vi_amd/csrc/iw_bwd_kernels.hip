@@ -11,7 +11,7 @@
 // the plain IWAE weights, whose gradient signal-to-noise falls with K (Rainforth et al. 2018).  At K = 1 it is
 // qbold_elbo_bwd's gradient of m nll + KL with the KL drawn at the likelihood's draw.
 //
-// Per draw, the likelihood-gradient passes 1 and 2 of elbo_bwd_kernel (restated, as refine_kernels.hip restates them;
+// Per draw, the likelihood-gradient passes 1 and 2 of elbo_bwd_kernel (its signal slopes are signal_grad.h's;
 // Gaussian or Student-t, linear or log data, either normalisation) and the KL draw's value and gradient: the whitened
 // form of iw_kernels.hip where the logit clip does not bind, elbo_bwd_kernel's general clipped-logit form (the clip
 // passes gradient) where it does.  The check is made per draw, so explicit normals equal to the Philox stream's give
@@ -31,6 +31,7 @@
 
 #include "elbo_core.h"
 #include "qbold_ctx.h"
+#include "signal_grad.h"
 
 // K <= QB_IW_BWD_LPV1_MAX_K: one lane per voxel; larger K: four.  Measured on 1 M voxels (MEASUREMENTS.md section 14):
 // one lane is 3.3x faster at K = 1, 2.2x (T = 11) / 2.1x (T = 24) at K = 8 and 8 % / 6 % at K = 32; beyond 32 the
@@ -45,36 +46,7 @@ int elbo_grid(const qbold_ctx* ctx);   // elbo_kernels.hip
 
 namespace {
 
-constexpr uint32_t kStreamIw = 6u;   // qbold_log_evidence_fwd's importance draws
 constexpr int kBlock = 256;
-
-struct FwdGrad {
-    float s, ds_doef, ds_ddbv;
-};
-
-// signal and its partials at tau index t (full model, table mode): elbo_bwd_kernels.hip's fwd_signal_grad
-__device__ __forceinline__ FwdGrad fwd_signal_grad(const qb::FwdLds* L, const QbDev& c,
-                                                   const qb::FwdFast& v, float oef, float dbv, int t) {
-    const float us = fmaf((float)t, v.ub, v.ua);
-    const float u = fabsf(us);
-    const int i = min((int)u, QB_TAB_SEG - 1);
-    const float f = u - (float)i;
-    const float4 k = L->tab[i];
-    const float F = fmaf(fmaf(fmaf(k.w, f, k.z), f, k.y), f, k.x);
-    const float ax = u * (1.0f / c.tab_inv_h);
-    const float dF = fmaf(fmaf(3.0f * k.w, f, 2.0f * k.z), f, k.y) * c.tab_inv_h + c.dF_node0 * ax;
-    const float e1 = qb::exp2f_(v.nd * F);
-    const float e2 = qb::exp2f_(v.ng * c.blood_B[t]);
-    const float tissue = v.tissue_w * e1, blood = v.blood_w * e2;
-    FwdGrad g;
-    g.s = tissue + blood;
-    const float inv_oef = qb::rcpf_(oef);
-    g.ds_doef = -dbv * dF * ax * inv_oef * tissue +
-                (2.0f * QB_LN2) * v.ng * c.blood_B[t] * inv_oef * blood;
-    const float dbw = c.include_blood ? c.m_bld_nb : 1.0f;
-    g.ds_ddbv = -F * tissue - dbw * c.e_te_r2t * e1 + (c.include_blood ? dbw * c.e_r2b_te * e2 : 0.0f);
-    return g;
-}
 
 // The whitened log q - log p of iw_kernels.hip (make_iw_kl): d + M z is a draw's residual under the prior.
 struct IwKl {
@@ -191,7 +163,7 @@ __device__ __forceinline__ void iw_bwd_draw(const qb::FwdLds* L, const QbDev& c,
         } else if (t == c.se_idx) {
             gs -= a1;
         }
-        const FwdGrad fg = fwd_signal_grad(L, c, fv, oef, dbv, t);
+        const qb::FwdGrad fg = qb::fwd_signal_grad(L, c, fv, oef, dbv, t);
         g_oef = fmaf(gs, fg.ds_doef, g_oef);
         g_dbv = fmaf(gs, fg.ds_ddbv, g_dbv);
     }
@@ -289,7 +261,7 @@ __global__ __launch_bounds__(kBlock) void iw_bwd_kernel(
         for (int g = part; 4 * g < K; g += LPV) {
             const int cnt = K - 4 * g < 4 ? K - 4 * g : 4;
             qb::DrawQuad dq;
-            if (!zv) dq.load(seed, vox, (uint32_t)g, kStreamIw);
+            if (!zv) dq.load(seed, vox, (uint32_t)g, qb::STREAM_IW);
 #pragma unroll 1
             for (int d = 0; d < cnt; ++d) {
                 float z0, z1;

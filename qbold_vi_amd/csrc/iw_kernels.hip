@@ -31,10 +31,7 @@ int elbo_grid(const qbold_ctx* ctx);
 
 namespace {
 
-// The Philox stream of the importance draws: 0 - 3 are qbold_dev.h's, 4 kl_mog's, 5 the dropout masks'.
-// qbold_normals(seed, 6, voxel0, K) reproduces the in-kernel draws exactly.
-constexpr uint32_t kStreamIw = 6u;
-
+// qbold_normals(seed, STREAM_IW, voxel0, K) reproduces the in-kernel importance draws exactly.
 constexpr int kBlock = 256;                                  // 4 waves
 constexpr int kVoxPerBlock = kBlock / QB_LANES_PER_VOXEL;    // 16 voxels per wave, 4 lanes each
 
@@ -117,7 +114,7 @@ __device__ __forceinline__ void iw_draws(const LDS* L, const QbDev& c, const qb:
             z1 = zv[2 * draw + 1];
         } else {
             if ((i & 3) == 0) {
-                dq.load(seed, vox, g, kStreamIw);
+                dq.load(seed, vox, g, qb::STREAM_IW);
                 g += QB_LANES_PER_VOXEL;
             }
             dq.next(z0, z1);
@@ -385,7 +382,7 @@ __global__ __launch_bounds__(kGenBlock) void iw_fwd_generic_kernel(
                     z1 = zv[2 * draw + 1];
                 } else {
                     if ((i & 3) == 0) {
-                        dq.load(seed, vox, g, kStreamIw);
+                        dq.load(seed, vox, g, qb::STREAM_IW);
                         g += QB_LANES_PER_VOXEL;
                     }
                     dq.next(z0, z1);
@@ -555,7 +552,7 @@ __device__ __forceinline__ void iw_draws_to_rows(const LDS* L, const QbDev& c, c
             z1 = zv[2 * draw + 1];
         } else {
             if ((i & 3) == 0) {
-                dq.load(seed, vox, g, kStreamIw);
+                dq.load(seed, vox, g, qb::STREAM_IW);
                 g += QB_LANES_PER_VOXEL;
             }
             dq.next(z0, z1);
@@ -709,7 +706,7 @@ __global__ __launch_bounds__(kGenBlock) void iw_draws_generic_kernel(
                     z1 = zv[2 * draw + 1];
                 } else {
                     if ((i & 3) == 0) {
-                        dq.load(seed, vox, g, kStreamIw);
+                        dq.load(seed, vox, g, qb::STREAM_IW);
                         g += QB_LANES_PER_VOXEL;
                     }
                     dq.next(z0, z1);

@@ -3,11 +3,12 @@
 // include/qbold_hip.h, qbold_laplace_posterior, states the definition (model, schedule, outputs) that the float64
 // reference of the tests restates; this file is its float32 form.
 //
-// Shape: elbo_bwd_generic_kernel<1>'s (elbo_bwd_kernels.hip; that kernel's text is frozen with its bits, so gen_signal
-// and the slope expressions are restated here instead of shared -- without node 0's slope, see lap_signal).  128
-// threads, one lane per voxel; the voxel's normalised data and 1 / sigma live in dynamic LDS as rows [t][thread] beside
-// FwdLds (8 T bytes per thread: 16.8 KiB per block at T = 11, 69.8 KiB at T = 64, two blocks per CU).  A thread owns its column of every row, so a wave's
-// access at a fixed t is 64 consecutive floats and no barrier is needed after the table fill.
+// Shape: the any-T refinement kernels' (refine_kernels.hip), with which this file shares the signal-with-slopes
+// evaluation and the per-thread LDS columns (signal_grad.h: sig_eval, slope_factors, VoxColumns) -- without node 0's
+// slope, see lap_signal.  128 threads, one lane per voxel; the voxel's normalised data and 1 / sigma live in dynamic LDS
+// as rows [t][thread] beside FwdLds (8 T bytes per thread: 16.8 KiB per block at T = 11, 69.8 KiB at T = 64, two blocks
+// per CU).  A thread owns its column of every row, so a wave's access at a fixed t is 64 consecutive floats and no
+// barrier is needed after the table fill.
 //
 // One evaluation = one pass over t that gathers F, g = J^T r and A = J^T J together.  The 1 or 3 images of the
 // normalisation window are evaluated first, value AND slopes, so that the pass forms each row of the Jacobian directly,
@@ -23,6 +24,7 @@
 
 #include "elbo_core.h"
 #include "qbold_ctx.h"
+#include "signal_grad.h"
 
 namespace qb {
 bool elbo_fast_path(const qbold_ctx* ctx);   // elbo_kernels.hip
@@ -47,35 +49,23 @@ struct LapArgs {
     float lambda0, lambda_up, inv_lambda_down, tol;
 };
 
-// signal and its partials with respect to (OEF, DBV) at tau index t: gen_signal + the slope expressions of
-// elbo_bwd_generic_kernel, restated.  The segment index is clamped: forward_transform bounds OEF by 0.84 and the table
-// spans OEF <= 1, so the clamp never binds for a finite point and keeps a NaN point inside the table.
+// signal and its partials with respect to (OEF, DBV) at tau index t.  The table's F drops Simpson node 0 (as the float32
+// reference's value does) and the slope here drops it too (SigEval::dFu alone, no n0 u^2 term), so that g is the
+// gradient of the F that the acceptance test compares -- unlike the training and refinement gradients, which restate
+// TF's autodiff and keep that node's slope (QbDev::dF_node0).
 struct LapSig {
     float s, ds_doef, ds_ddbv;
 };
 struct LapPoint {
     qb::FwdFast fv;
-    float ko, kb, kd1, kd2;
+    qb::SlopeFactors k;
 };
 __device__ __forceinline__ LapSig lap_signal(const qb::FwdLds* L, const LapPoint& p, int t) {
-    const float u = fabsf(fmaf((float)t, p.fv.ub, p.fv.ua));
-    const int i = min(max((int)u, 0), QB_TAB_SEG - 1);
-    const float f = __builtin_amdgcn_fractf(u);
-    const float4 k = L->tab[i];
-    const float F = fmaf(fmaf(fmaf(k.w, f, k.z), f, k.y), f, k.x);
-    const float e1 = qb::exp2f_(p.fv.nd * F);
-    const float B = L->blood_B[t];
-    const float e2 = qb::exp2f_(p.fv.ng * B);
-    const float tissue = p.fv.tissue_w * e1, blood = p.fv.blood_w * e2;
-    // |x| dF/dx at x = u / tab_inv_h, the cubic's own slope: d|x| / d oef = |x| / oef.  The table's F drops Simpson
-    // node 0 (as the float32 reference's value does) and its slope here drops it too, so that g is the gradient of the
-    // F that the acceptance test compares -- unlike the training gradients, which restate TF's autodiff and keep that
-    // node's slope (QbDev::dF_node0).
-    const float dFu = fmaf(fmaf(3.0f * k.w, f, 2.0f * k.z), f, k.y) * u;
+    const qb::SigEval e = qb::sig_eval(L, p.fv, t);
     LapSig g;
-    g.s = tissue + blood;
-    g.ds_doef = fmaf(p.ko * dFu, tissue, p.kb * B * blood);
-    g.ds_ddbv = fmaf(p.kd2, e2, -fmaf(F, tissue, p.kd1 * e1));
+    g.s = e.s;
+    g.ds_doef = e.ds_doef(p.k, e.dFu());
+    g.ds_ddbv = e.ds_ddbv(p.k);
     return g;
 }
 
@@ -84,28 +74,14 @@ struct LapEval {
     float F, chi2, band, ga, gb, aaa, aab, abb;
 };
 
-struct LapVoxel {
-    const qb::FwdLds* L;
-    const float* yt;   // this thread's column: yt[t * kLapBlock]
-    const float* is;
-    int T, w_lo, w_hi;
-    float w_se, dbw;
-};
-
-__device__ __forceinline__ LapEval lap_eval(const QbDev& c, const LapVoxel& vx, const qb::LogitMvn& pm, float a,
+__device__ __forceinline__ LapEval lap_eval(const QbDev& c, const qb::VoxColumns& vx, const qb::LogitMvn& pm, float a,
                                             float b) {
     const float sa = qb::sigmoidf_(a), sb = qb::sigmoidf_(b);
     const float oef = sa * QB_OEF_RANGE + QB_MIN_OEF;
     const float dbv = sb * QB_DBV_RANGE + QB_MIN_DBV;
     LapPoint p;
     p.fv = qb::fwd_fast(c, oef, dbv);
-    const float inv_oef = qb::rcpf_(oef);
-    // per-point factors of the slopes: tissue exp(-dbv F(x)), x proportional to oef; blood exp(-g B), g proportional
-    // to oef^2; weights tissue_w = (1 - bw) C1, blood_w = bw C2, bw = dbw dbv
-    p.ko = -dbv * inv_oef;
-    p.kb = (2.0f * QB_LN2) * p.fv.ng * inv_oef;
-    p.kd1 = vx.dbw * c.e_te_r2t;
-    p.kd2 = c.include_blood ? vx.dbw * c.e_r2b_te : 0.0f;
+    p.k = qb::slope_factors(c, p.fv, oef, dbv, vx.dbw);
     // the normaliser n and its slopes over the window (1 or 3 images, wave-uniform)
     float ns = 0.0f, no = 0.0f, nd = 0.0f;
     for (int t = vx.w_lo; t <= vx.w_hi; ++t) {
@@ -175,23 +151,19 @@ __global__ __launch_bounds__(kLapBlock) void laplace_kernel(
     extern __shared__ __align__(16) unsigned char smem[];
     qb::FwdLds* L = reinterpret_cast<qb::FwdLds*>(smem);
     const int T = c.T, se = c.se_idx;
-    // this thread's column of the two rows
+    // this thread's column of the two rows, set up ahead of the table fill: through vox_columns (after the fill, as the
+    // refinement kernels have it, or here) the kernel comes out with one to four more address additions
     float* yt = reinterpret_cast<float*>(smem + sizeof(qb::FwdLds)) + threadIdx.x;
     float* is = yt + T * kLapBlock;
     qb::fwd_lds_fill(L, g_tab, false);
     if (threadIdx.x < QB_MAX_T) L->blood_B[threadIdx.x] = c.blood_B[threadIdx.x];
     __syncthreads();
 
-    LapVoxel vx;
+    qb::VoxColumns vx;
+    qb::vox_window(c, vx);
     vx.L = L;
     vx.yt = yt;
     vx.is = is;
-    vx.T = T;
-    // normalisation window (model.py:541-545) and the weight of each of its images
-    vx.w_lo = c.multi_norm ? se - 1 : se;
-    vx.w_hi = c.multi_norm ? se + 1 : se;
-    vx.w_se = c.multi_norm ? 1.0f / 3.0f : 1.0f;
-    vx.dbw = c.include_blood ? c.m_bld_nb : 1.0f;
 
     const int64_t ntile = (N + kLapBlock - 1) / kLapBlock;
     for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {

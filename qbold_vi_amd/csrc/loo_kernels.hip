@@ -41,7 +41,6 @@ int elbo_grid(const qbold_ctx* ctx);
 
 namespace {
 
-constexpr uint32_t kStreamIw = 6u;   // iw_kernels.hip's stream: draw k here is draw k of qbold_log_evidence_draws
 constexpr int kRowsBlock = 128;
 constexpr int kRowsVox = kRowsBlock / QB_LANES_PER_VOXEL;   // 32 voxels per block
 constexpr int kFinWaves = 4;
@@ -177,7 +176,7 @@ __global__ __launch_bounds__(kRowsBlock) void loo_rows_kernel(
             // never stored)
             LooDraw<FAST> dr[4];
             qb::DrawQuad dq;
-            if (!zv) dq.load(seed, vox, (uint32_t)g, kStreamIw);
+            if (!zv) dq.load(seed, vox, (uint32_t)g, qb::STREAM_IW);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float z0, z1;

@@ -34,9 +34,7 @@ int elbo_grid(const qbold_ctx* ctx);
 
 namespace {
 
-// The Philox stream of the predictive draws: 0 - 3 are qbold_dev.h's, 4 kl_mog's, 5 dropout's, 6 IW's, 7 refine's.
-// qbold_normals(seed, 8, voxel0, L) reproduces the in-kernel draws exactly.
-constexpr uint32_t kStreamPpc = 8u;
+// qbold_normals(seed, STREAM_PPC, voxel0, L) reproduces the in-kernel predictive draws exactly.
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 
@@ -262,7 +260,7 @@ __global__ __launch_bounds__(kBlock) void ppc_kernel(
                 z0 = zv[2 * l];
                 z1 = zv[2 * l + 1];
             } else {
-                if ((l & 3) == 0) dq.load(seed, vox, (uint32_t)(l >> 2), kStreamPpc);
+                if ((l & 3) == 0) dq.load(seed, vox, (uint32_t)(l >> 2), qb::STREAM_PPC);
                 dq.next(z0, z1);
             }
             float a, b, oef, dbv;
@@ -362,7 +360,7 @@ __global__ __launch_bounds__(kBlock) void ppc_generic_kernel(
                 z0 = zv[2 * l];
                 z1 = zv[2 * l + 1];
             } else {
-                if ((l & 3) == 0) dq.load(seed, vox, (uint32_t)(l >> 2), kStreamPpc);
+                if ((l & 3) == 0) dq.load(seed, vox, (uint32_t)(l >> 2), qb::STREAM_PPC);
                 dq.next(z0, z1);
             }
             float a, b, oef, dbv;

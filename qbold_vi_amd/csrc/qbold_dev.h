@@ -229,7 +229,19 @@ __device__ __forceinline__ void box_muller16(uint32_t w, float& z0, float& z1) {
 }
 #define QB_BM_K 1.1774100225154747f   // sqrt(2 ln 2): z = QB_BM_K sqrt(-log2 u1) (cos, sin)
 
-enum { STREAM_LIK = 0, STREAM_KL = 1, STREAM_MOMENTS = 2, STREAM_R2P = 3 };
+// The registry of Philox streams (the last word of the counter): independent normals rest on these ids never colliding,
+// so every user of philox4x32_7 takes its id from here.
+enum {
+    STREAM_LIK = 0,       // likelihood draws of the ELBO kernels
+    STREAM_KL = 1,        // their Monte-Carlo KL draws
+    STREAM_MOMENTS = 2,   // calculate_means
+    STREAM_R2P = 3,       // the R2' moments
+    STREAM_KL_MOG = 4,    // qbold_kl_mog: one pair per voxel
+    STREAM_DROPOUT = 5,   // the training kernels' dropout masks
+    STREAM_IW = 6,        // importance draws: qbold_log_evidence_fwd / _draws and everything that replays them
+    STREAM_REFINE = 7,    // the refinement steps' likelihood draws
+    STREAM_PPC = 8,       // posterior predictive draws
+};
 
 // The four draws of Philox call `quad` of a stream, served one at a time: the words stay words until a draw is taken
 // (four live registers instead of eight normals, and the Box-Muller code sits once in a draw loop that is not unrolled).

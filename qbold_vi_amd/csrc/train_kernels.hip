@@ -2947,7 +2947,7 @@ constexpr float kLnEps = 1e-3f;   // tfa GroupNormalization's default epsilon
 __device__ __forceinline__ float drop_factor(const NormSpec& sp, int64_t row, int col) {
     if (sp.drop_thresh == 0u) return 1.0f;
     const uint4 o = qb::philox4x32_7(make_uint4((uint32_t)row, (uint32_t)((uint64_t)row >> 32),
-                                                (uint32_t)(col >> 3) | (sp.layer << 16), 5u),
+                                                (uint32_t)(col >> 3) | (sp.layer << 16), qb::STREAM_DROPOUT),
                                      make_uint2((uint32_t)sp.seed, (uint32_t)(sp.seed >> 32)));
     const uint32_t w = ((col >> 1) & 3) == 0 ? o.x : ((col >> 1) & 3) == 1 ? o.y : ((col >> 1) & 3) == 2 ? o.z : o.w;
     const uint32_t hw = (col & 1) ? (w >> 16) : (w & 0xffffu);
