@@ -427,12 +427,32 @@ int qbold_log_evidence_fwd(const qbold_ctx* ctx, const float* x, const float* ma
  *     normaliser qbold_encoder_train_bwd / qbold_encoder_spatial_bwd read
  *   workspace: qbold_elbo_workspace_bytes() bytes.
  * Fixed-order sums, no atomics: a voxel's outputs are the same bits at any batch position, under any sharding by voxel0
- * and run to run.  Full signal model in table mode, T = 11 or 24 (qbold_elbo_bwd's other protocols are not built here), the use_mvg = True family;
+ * and run to run.  Full signal model in table mode, T = 11 or 24 with every likelihood switch (every other protocol:
+ * qbold_log_evidence_bwd_anyt below), the use_mvg = True family;
  * QBOLD_ERR_UNSUPPORTED otherwise.  QBOLD_ERR_INVALID for K < 1, K > QBOLD_IW_MAX_K or a NULL required buffer. */
 int qbold_log_evidence_bwd(const qbold_ctx* ctx, const float* x, const float* mask, const float* q,
                            const float* prior, const float* log_sigma, const float* z, int K, uint64_t seed,
                            int64_t voxel0, float* g_q, float* g_log_sigma, float* out, double* sums,
                            void* workspace, int64_t N, void* stream);
+
+/* qbold_log_evidence_bwd on any tau grid, 1 <= T <= 64 (run-time-T kernel: the voxel's normalised data, 1 / sigma and
+ * its T sigma sums in LDS, the streaming log-sum-exp and the five DReG sums in registers).  Arguments, draws (Philox
+ * stream 6 or z: draw k is draw k of qbold_log_evidence_fwd), the lane mapping by K, outputs, masked voxels, sums,
+ * workspace, the bitwise properties and the QBOLD_ERR_INVALID cases are those of qbold_log_evidence_bwd, which is
+ * unchanged: it keeps its T = 11 / 24 kernels, their bits, and QBOLD_ERR_UNSUPPORTED for every other T.
+ *   This entry takes T = 11 and 24 too and runs the run-time-T kernel there: the same function on the same draws,
+ *   the likelihood-gradient sums regrouped (one pass over the taus per draw), so it agrees with the specialised
+ *   kernels to rounding, not to the bit.
+ *   Configurations: those of the any-T forward and of qbold_elbo_bwd at these T -- full signal model, table mode,
+ *   Gaussian likelihood on linear data, either normalisation, the spin echo on or off the grid.
+ *   Traffic per voxel: 4 (2 T + 10 + 1) B in (+ 8 K B of z when given), 4 (T + 5) B out (+ 12 with out); with K > 32
+ *   the four lanes of a voxel repeat the reads.
+ * QBOLD_ERR_UNSUPPORTED for a context without the full signal model, for the literal tissue mode, and for the
+ * Student-t likelihood or log data (qbold_log_evidence_bwd has those at T = 11 / 24). */
+int qbold_log_evidence_bwd_anyt(const qbold_ctx* ctx, const float* x, const float* mask, const float* q,
+                                const float* prior, const float* log_sigma, const float* z, int K, uint64_t seed,
+                                int64_t voxel0, float* g_q, float* g_log_sigma, float* out, double* sums,
+                                void* workspace, int64_t N, void* stream);
 
 /* The per-draw rows behind qbold_log_evidence_fwd, unreduced (this package's addition): the K draws of that entry
  * (explicit z [N][K][2], or the Philox stream 6 keyed (seed, voxel0 + i): draw k of this call is draw k there) and per

@@ -144,6 +144,7 @@ SIGNATURES = {
                                    C.c_double, C.c_double, _I64, _P]),
     "qbold_log_evidence_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
     "qbold_log_evidence_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _P, _I64, _P]),
+    "qbold_log_evidence_bwd_anyt": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _P, _I64, _P]),
     "qbold_log_evidence_draws": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _I64, _P]),
     "qbold_psis": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _I64, _P]),
     "qbold_posterior_grid": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GridCfg), _P, _P, _P, _P, _I64, _P]),

@@ -515,12 +515,28 @@ class Context:
                    "qbold_log_evidence_fwd")
         return sums, out, means
 
-    def log_evidence_bwd(self, x, mask, q, prior, log_sigma, K, z=None, seed=1, voxel0=0, want_out=False):
+    def _log_evidence_bwd_entry(self, kernel):
+        """The C entry log_evidence_bwd runs, chosen as _refine_entry chooses: the specialised kernels' at the
+        reference's 11 / 24 taus (their bits are pinned), the run-time-T kernel's on every other grid or when
+        kernel = "generic"."""
+        if kernel not in ("auto", "generic"):
+            raise ValueError("log_evidence_bwd: kernel must be 'auto' or 'generic'")
+        name = "qbold_log_evidence_bwd"
+        return name if kernel == "auto" and self.T in (11, 24) else name + "_anyt"
+
+    def log_evidence_bwd(self, x, mask, q, prior, log_sigma, K, z=None, seed=1, voxel0=0, want_out=False,
+                         kernel="auto"):
         """Head gradients of the per-voxel negative importance-weighted bound -log p^_K (qbold_log_evidence_bwd; the K
         draws of log_evidence for the same seed, Philox stream 6 unless z [N, K, 2] is given): the doubly-reparameterised
         gradient for q, the exact one for log_sigma (the sigma head before exp), both unnormalised by sum(mask) like
-        elbo_bwd's.  Returns (sums double[3] device tensor = (sum [m>0] m (-log p^), sum [m>0] m (-ELBO_same),
+        elbo_bwd's.
+        kernel: "auto" runs the kernels specialised for the reference's 11 / 24 taus there and the run-time-T kernel
+        (qbold_log_evidence_bwd_anyt, 1 <= T <= 64; Gaussian likelihood on linear data) on every other grid; "generic"
+        runs the run-time-T kernel at any T (at 11 / 24 taus it agrees with the specialised kernels to rounding, not to
+        the bit).
+        Returns (sums double[3] device tensor = (sum [m>0] m (-log p^), sum [m>0] m (-ELBO_same),
         sum [m>0] m), g_q [N, 5], g_log_sigma [N, T], out [N, 3] = (log p^, same-draw ELBO, ESS) or None)."""
+        entry = self._log_evidence_bwd_entry(kernel)
         x = _f32(x, "x", self.T)
         N = x.numel() // self.T
         q = _f32(q, "q", 5)
@@ -534,10 +550,9 @@ class Context:
         gq = torch.empty((N, 5), dtype=torch.float32, device=x.device)
         gls = torch.empty((N, self.T), dtype=torch.float32, device=x.device)
         out = torch.empty((N, 3), dtype=torch.float32, device=x.device) if want_out else None
-        _lib.check(self.lib.qbold_log_evidence_bwd(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior), _ptr(ls),
-                                                   _ptr(z), int(K), int(seed), int(voxel0), _ptr(gq), _ptr(gls),
-                                                   _ptr(out), _ptr(sums), _ptr(self._workspace()), N, _stream()),
-                   "qbold_log_evidence_bwd")
+        _lib.check(getattr(self.lib, entry)(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior), _ptr(ls),
+                                            _ptr(z), int(K), int(seed), int(voxel0), _ptr(gq), _ptr(gls),
+                                            _ptr(out), _ptr(sums), _ptr(self._workspace()), N, _stream()), entry)
         return sums, gq, gls, out
 
     def log_evidence_draws(self, x, mask, q, prior, sigma, K, z=None, seed=1, voxel0=0, want_theta=False):

@@ -281,6 +281,24 @@ def main():
                 lambda: ctx.refine_posterior_spatial(*vol1m[:5], 5.0, steps=200, S=1, kernel="generic"),
                 200 * sbytes(T)),
         })
+    # head gradients of the importance-weighted bound on any tau grid (iw_bwd_generic_kernel): 33 and 64 taus (the
+    # Laplace rows' protocols, the T = 11 encoder's heads, sigma = 0.05) at K = 8 / 32 (one lane per voxel) and 64
+    # (four), and kernel="generic" at 11 / 24 taus beside the specialised kernels' log_evidence_bwd rows above
+    def iw_bwd_anyt_rows(name, p):
+        c = Context(p, True, True)
+        xs = c.signal_fwd(y)
+        lss = torch.log(torch.full((n, c.T), 0.05, device="cuda"))
+        return {f"log_evidence_bwd(T={name},K={K})": (
+            lambda K=K: c.log_evidence_bwd(xs, mask, q, o1, lss, K, seed=1), 12 * c.T + 64) for K in (8, 32, 64)}
+    if not only_names() or any("log_evidence_bwd" in o or "generic" in o for o in only_names()):
+        calls.update(iw_bwd_anyt_rows("33", dict(params, tau_start="-0.008", tau_end="0.057", tau_step="0.002")))
+        calls.update(iw_bwd_anyt_rows("64", dict(params, tau_start="-0.008", tau_end="0.0555", tau_step="0.001")))
+        for K in (8, 32):
+            calls[f"log_evidence_bwd(T=11,K={K},generic)"] = (
+                lambda K=K: ctx.log_evidence_bwd(x, mask, q, o1, ls, K, seed=1, kernel="generic"), 12 * T + 64)
+            calls[f"log_evidence_bwd(T=24,K={K},generic)"] = (
+                lambda K=K: ctx24.log_evidence_bwd(x24, mask, q, o1, torch.log(sg24), K, seed=1, kernel="generic"),
+                12 * 24 + 64)
     only = only_names()
     out = {}
     for name, (fn, bpv) in calls.items():

@@ -16,11 +16,13 @@ from qbold_vi_amd.training import get_params  # noqa: E402
 
 
 def measure(voxels=1 << 20, crops=(38, 25, 25, 8), steps=10, S=1, K=70, graph=True, only=None, ksel=0,
-            config_dir="config", iw_samples=0):
+            config_dir="config", iw_samples=0, protocol=None):
     """ms per fine-tuning step on a voxel batch and on a crop batch (bench.py embeds this in its JSON line).
-    iw_samples > 0: the step of iw_samples fine-tuning (qbold_log_evidence_bwd instead of qbold_elbo_bwd)."""
+    iw_samples > 0: the step of iw_samples fine-tuning (qbold_log_evidence_bwd, or qbold_log_evidence_bwd_anyt off the
+    reference's 11 / 24 taus, instead of qbold_elbo_bwd).  protocol: (tau_start [s], tau_step [s], T) instead of the
+    config's tau grid."""
     a = argparse.Namespace(voxels=voxels, crops=list(crops), steps=steps, S=S, K=K, graph=graph, only=only, ksel=ksel,
-                           iw_samples=iw_samples)
+                           iw_samples=iw_samples, protocol=protocol)
     return _run(a, config_dir)
 
 
@@ -36,12 +38,19 @@ def main():
     ap.add_argument("--ksel", type=int, default=0, help="qbold_ctx_set_kernel_selection mask (QBOLD_KSEL_* of include/qbold_hip.h)")
     ap.add_argument("--iw-samples", type=int, default=0, dest="iw_samples",
                     help="K > 0: head gradients of the K-sample importance-weighted bound (training's iw_samples)")
+    ap.add_argument("--protocol", nargs=3, default=None, metavar=("TAU_START", "TAU_STEP", "T"),
+                    help="a tau grid instead of the config's: start and step in seconds and the number of taus, "
+                         "e.g. -0.008 0.002 33")
     a = ap.parse_args()
     print(json.dumps(_run(a, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "config"))))
 
 
 def _run(a, config_dir):
     params = get_params(config_dir)
+    if a.protocol:
+        start, step, T = float(a.protocol[0]), float(a.protocol[1]), int(a.protocol[2])
+        params = dict(params, tau_start=str(start), tau_end=str(start + step * T - step / 2), tau_step=str(step),
+                      tau_weighted="False")
     ctx = Context(params, True, True)
     if a.ksel:
         ctx.set_kernel_selection(a.ksel)
@@ -49,7 +58,7 @@ def _run(a, config_dir):
                              im_loss_sigma=0.05, seed=1, spatial_taps=9)
     ew = EncoderWeights(ctx, ctx.T, 60, 2, True, -3.0, spatial_taps=9).set_from_arrays(w)
     st = TrainState(ctx, ew)
-    out = {}
+    out = dict(T=ctx.T) if a.protocol else {}
 
     def timed(fn):
         import time
