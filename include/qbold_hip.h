@@ -686,6 +686,33 @@ int qbold_laplace_posterior(const qbold_ctx* ctx, const float* x, const float* m
                             const float* sigma, const float* u0, const qbold_laplace_cfg* cfg,
                             float* q_out, float* out, int64_t N, void* stream);
 
+/* Adaptive importance sampling per voxel by moment matching (this package's addition; Paananen, Piironen, Buerkner &
+ * Vehtari 2021 and the population Monte Carlo family): `rounds` rounds of K draws from the current proposal, each
+ * weighted as qbold_log_evidence_fwd weights them, after each of which the proposal's mean and covariance move to the
+ * weighted ones (shrunk by lambda = ESS / (ESS + shrink)); the proposal of the round with the largest ESS comes back as
+ * raw heads that every entry taking q accepts.  qbold_vi_amd/csrc/adapt_kernels.hip states the algorithm in full in its
+ * head; tests/_adapt_reference.py restates it in float64.
+ *   q [N][5]: the starting heads (the encoder's, qbold_laplace_posterior's, or the prior's own row).  z [N][rounds K][2]
+ *   explicit normals or NULL: draw r K + k of qbold_normals(seed, 9, voxel0 + i, rounds K) (Philox stream 9).
+ *   q_out [N][5]; out [N][2 rounds + 2] = (log p^_r, ESS_r) per round, the returned round's index, flags (bit 0 a round
+ *   skipped for non-finite weights, bit 1 a mean reached the logit clip, bit 2 a spread head was clamped -- bits 1 and 2
+ *   as qbold_laplace_posterior's); q_rounds [N][rounds][5] or NULL: every round's proposal as raw heads (row 0 and a
+ *   returned round 0 are the given heads bit for bit).  Voxels with mask <= 0 (or NaN) are not read: q_out is q's row,
+ *   out and q_rounds rows are NaN.  No atomics, no workspace, no sums: a voxel's outputs are the same bits in any batch
+ *   at any position (with voxel0 following it).  One run-time-T kernel serves every 1 <= T <= 64.
+ * Full signal model in table mode, Gaussian likelihood on linear data, either normalisation, any spin-echo index;
+ * QBOLD_ERR_UNSUPPORTED otherwise.  QBOLD_ERR_INVALID for rounds outside 1 .. 16, K outside 8 .. 1024 or no multiple of
+ * 4, a shrink that is not positive and finite, N < 0 or a NULL required buffer (cfg, q_out, out; x, q, prior, sigma
+ * when N > 0); these are checked first.  N = 0 returns QBOLD_OK without a launch. */
+typedef struct { int rounds; int K; float shrink; } qbold_adapt_cfg;
+#define QBOLD_ADAPT_MAX_ROUNDS 16
+#define QBOLD_ADAPT_MIN_K 8
+#define QBOLD_ADAPT_MAX_K 1024
+int qbold_adapt_posterior(const qbold_ctx* ctx, const float* x, const float* mask, const float* q, const float* prior,
+                          const float* sigma, const float* z /* nullable */, const qbold_adapt_cfg* cfg, uint64_t seed,
+                          int64_t voxel0, float* q_out, float* out, float* q_rounds /* nullable */, int64_t N,
+                          void* stream);
+
 /* Posterior predictive checks of the fine-tuning model per voxel (this package's addition; the reference has no
  * counterpart): Gelman, Meng & Stern 1996 for the p-value, Watanabe 2010 / Vehtari, Gelman & Gabry 2017 for lppd and
  * WAIC.  theta_l, l = 0 .. L-1: the reparameterised draws of q (heads [N][5], the use_mvg = True family), from explicit

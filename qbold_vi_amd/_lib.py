@@ -23,6 +23,9 @@ QBOLD_LOO_OUT = 6     # columns of qbold_loo's out
 QBOLD_CAL_OUT = 6     # columns of qbold_calibration's out
 QBOLD_CAL_MAX_L = 1 << 20
 QBOLD_LAPLACE_OUT = 15   # columns of qbold_laplace_posterior's out
+QBOLD_ADAPT_MAX_ROUNDS = 16   # qbold_adapt_posterior
+QBOLD_ADAPT_MIN_K = 8
+QBOLD_ADAPT_MAX_K = 1024
 
 
 class QboldError(RuntimeError):
@@ -65,6 +68,11 @@ class LaplaceCfg(C.Structure):
     """qbold_laplace_cfg: the Levenberg-Marquardt schedule of qbold_laplace_posterior."""
     _fields_ = [("max_iter", C.c_int32), ("lambda0", C.c_float), ("lambda_up", C.c_float), ("lambda_down", C.c_float),
                 ("tol", C.c_float)]
+
+
+class AdaptCfg(C.Structure):
+    """qbold_adapt_cfg: rounds of K draws each; lambda = ESS / (ESS + shrink)."""
+    _fields_ = [("rounds", C.c_int32), ("K", C.c_int32), ("shrink", C.c_float)]
 
 
 class Geometry(C.Structure):
@@ -149,6 +157,8 @@ SIGNATURES = {
     "qbold_psis": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _I64, _P]),
     "qbold_posterior_grid": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GridCfg), _P, _P, _P, _P, _I64, _P]),
     "qbold_laplace_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(LaplaceCfg), _P, _P, _I64, _P]),
+    "qbold_adapt_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(AdaptCfg), _U64, _I64, _P, _P, _P, _I64,
+                                        _P]),
     "qbold_posterior_predictive": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
     "qbold_loo_workspace_bytes": (_I64, [_P, C.c_int, _I64]),
     "qbold_loo": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _P, _P, _I64, _P]),

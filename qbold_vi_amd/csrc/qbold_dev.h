@@ -241,6 +241,7 @@ enum {
     STREAM_IW = 6,        // importance draws: qbold_log_evidence_fwd / _draws and everything that replays them
     STREAM_REFINE = 7,    // the refinement steps' likelihood draws
     STREAM_PPC = 8,       // posterior predictive draws
+    STREAM_ADAPT = 9,     // qbold_adapt_posterior: round r's draws are draws r K .. r K + K - 1
 };
 
 // The four draws of Philox call `quad` of a stream, served one at a time: the words stay words until a draw is taken

@@ -476,6 +476,43 @@ class FineTuner:
                     r2p_sd=col(10), log_evidence=col(11), chi2=col(12), iterations=col(13),
                     converged=(live & ((flags & 1) == 0)).reshape(lead), on_clip=bit(1), clamped=bit(2))
 
+    def adapt(self, data, mask, prior, q=None, rounds=6, no_samples=64, shrink=4.0, seed=1, voxel0=0):
+        """Adaptive importance sampling per voxel by moment matching (Context.adapt_posterior; Paananen et al. 2021):
+        `rounds` rounds of `no_samples` draws, after each of which the proposal moves to the importance-weighted mean
+        and covariance of its own draws (the mass-covering forward-KL projection, shrunk by ESS / (ESS + shrink)) --
+        the remedy for voxels whose log_evidence(psis=True) k^ says the importance estimates cannot be trusted.  Starts
+        from the encoder heads of encoder_model.predict, from given heads q [..., 5] (laplace()'s or refine()'s), or,
+        q = "prior", from the prior itself (no encoder heads involved, as laplace(start="prior")); sigma as refine()
+        takes it.  Shaped like the data's spatial dims:
+          q [..., 5] (raw heads of the round with the largest ESS: goes unchanged to calculate_means, elbo(q=...),
+            log_evidence(q=..., psis=True), posterior_grid(q=...), posterior_predictive(q=...), loo, calibration)
+          log_evidence, ess [..., rounds] (each round's log p^ and ESS of no_samples), best (the returned round),
+          flags (int32: 1 a round skipped for non-finite weights, 2 a mean on the logit clip, 4 a spread head clamped)
+        Voxels outside the mask keep their starting heads and are NaN (best -1, flags 0)."""
+        tr = self._trainer
+        self._check_mvn_family("adapt")
+        T = data.shape[-1]
+        x = _flat(data, T)
+        m = None if mask is None else mask.reshape(-1)
+        p5 = _flat(prior, prior.shape[-1]).contiguous()
+        if isinstance(q, str):
+            if q != "prior":
+                raise ValueError("adapt: q must be heads [..., 5], None (the encoder's) or 'prior'")
+            _, sg = self._heads_and_sigma(data)
+            q0 = p5
+        else:
+            q0, sg = self._heads_and_sigma(data, q)
+        q_out, out = tr._ctx.adapt_posterior(x, m, q0, p5, sg, rounds=rounds, K=no_samples, shrink=shrink, seed=seed,
+                                             voxel0=voxel0)
+        lead = data.shape[:-1]
+        R = (out.shape[1] - 2) // 2
+        live = ~torch.isnan(out[:, 2 * R])
+        best = torch.where(live, torch.nan_to_num(out[:, 2 * R], nan=0.0).to(torch.int32),
+                           torch.full_like(out[:, 0], -1, dtype=torch.int32))
+        flags = torch.nan_to_num(out[:, 2 * R + 1], nan=0.0).to(torch.int32)
+        return dict(q=q_out.reshape(lead + (5,)), log_evidence=out[:, 0:2 * R:2].reshape(lead + (R,)),
+                    ess=out[:, 1:2 * R:2].reshape(lead + (R,)), best=best.reshape(lead), flags=flags.reshape(lead))
+
     def posterior_predictive(self, data, mask, q=None, no_samples=256, seed=1, voxel0=0, want_curves=False):
         """Posterior predictive checks of `no_samples` = L draws per voxel (Context.posterior_predictive) for the heads q
         [..., 5] (None: the encoder heads of encoder_model.predict; refine()'s output, say) and the sigma that goes with
@@ -924,7 +961,7 @@ class EncoderTrainer:
     def save_predictions(self, model, data, filename, transform_directory=None, use_first_op=True,
                          fine_tuner_model=None, priors=None, iw_samples=None, refine_steps=None,
                          posterior_grid=None, ppc_samples=None, refine_smoothness_weight=0.0, psis=False,
-                         loo_samples=None, laplace=False):
+                         loo_samples=None, laplace=False, adapt_rounds=None):
         """model.py:772-887: write `<filename>_{oef,dbv,r2p,logstds}.nii.gz` (posterior means of
         OEF / DBV / R2' over 200 draws and their variances) and, with a fine tuner,
         `_likelihood` (per-voxel NLL averaged over 100 stochastic passes), `_kl` (100-draw KL to
@@ -961,6 +998,11 @@ class EncoderTrainer:
         `_oef_laplace`, `_dbv_laplace`, `_r2p_laplace`, `_oefsd_laplace`, `_dbvsd_laplace`, `_logevidence_laplace`,
         `_chi2` and `_laplaceflags` (bit 0 not converged, bit 1 on the logit clip, bit 2 heads clamped), zero outside
         the mask; these maps join the returned dict.
+        adapt_rounds = R (with a fine tuner; this package's addition, default None writes nothing new): R rounds of
+        adaptive importance sampling from the encoder's heads (FineTuner.adapt, 64 draws per round) as `_oef_adapt`,
+        `_dbv_adapt`, `_r2p_adapt` (calculate_means of the adapted heads) and `_ess_adapt` (the returned round's ESS
+        over its draws, in (0, 1]), zero outside the mask; with iw_samples (and psis) the importance maps above are
+        taken under the adapted heads, so `_khat` is theirs.  These maps join the returned dict.
         data [subj, X, Y, Z, T+1] with the mask last; each map is stored as [X, Y, Z, subj*C].
         `transform_directory/example.nii.gz`, when present, donates its header (:794-797); the
         FSL `applywarp`/`fslmerge` MNI step (:850-879) is preprocessing outside this package and
@@ -969,6 +1011,8 @@ class EncoderTrainer:
         from . import nifti
         if laplace and not fine_tuner_model:
             raise ValueError("save_predictions(laplace=True) needs a fine tuner (its sigma and the prior maps)")
+        if adapt_rounds and not fine_tuner_model:
+            raise ValueError("save_predictions(adapt_rounds=R) needs a fine tuner (its sigma and the prior maps)")
         data = torch.as_tensor(data, dtype=torch.float32, device=self._ctx.device)
         T = self._ctx.T
         mask = data[..., -1:]
@@ -1011,12 +1055,28 @@ class EncoderTrainer:
             save_im_data((y_true - y_pred).abs().mean(-1, keepdim=True), filename + '_residual')
 
         iw_maps = None
+        q_adapt = ad_maps = None
+        if fine_tuner_model and adapt_rounds:
+            K_ad = 64   # draws per round
+            ad = fine_tuner_model.adapt(data[..., :-1], mask, torch.as_tensor(priors, device=data.device)[..., :self._nq],
+                                        rounds=int(adapt_rounds), no_samples=K_ad, seed=self._seed + 61)
+            q_adapt = ad["q"]
+            live = mask[..., 0] > 0
+            ess = torch.gather(torch.nan_to_num(ad["ess"]), -1, ad["best"].clamp(min=0).long()[..., None])[..., 0] / K_ad
+            a_means = self.calculate_means(q_adapt, None, include_r2p=True, no_samples=200)
+            a_means = torch.where(live[..., None], a_means, torch.zeros_like(a_means))
+            zero = torch.zeros_like(ess)
+            ad_maps = {"oef_adapt": a_means[..., 0:1], "dbv_adapt": a_means[..., 1:2], "r2p_adapt": a_means[..., 2:3],
+                       "ess_adapt": torch.where(live, ess, zero)[..., None]}
+            for k, v in ad_maps.items():
+                save_im_data(v, filename + '_' + k)
         if psis and not (fine_tuner_model and iw_samples):
             raise ValueError("save_predictions(psis=True) smooths the draws of iw_samples: give a fine tuner and iw_samples")
         if fine_tuner_model and iw_samples:
             iw = fine_tuner_model.log_evidence(data[..., :-1], mask,
                                                torch.as_tensor(priors, device=data.device)[..., :self._nq],
-                                               no_samples=int(iw_samples), seed=self._seed + 31, psis=bool(psis))
+                                               no_samples=int(iw_samples), seed=self._seed + 31, psis=bool(psis),
+                                               q=q_adapt)
             live = mask[..., 0] > 0
             zero = torch.zeros_like(iw["log_evidence"])
             iw_maps = {k: torch.where(live, v, zero)[..., None] for k, v in
@@ -1029,6 +1089,8 @@ class EncoderTrainer:
                                  ("dbv_psis", iw["psis_means"][..., 1]), ("r2p_psis", iw["psis_means"][..., 2]))})
             for k, v in iw_maps.items():
                 save_im_data(v, filename + '_' + k)
+        if ad_maps:
+            iw_maps = dict(ad_maps, **(iw_maps or {}))
 
         if fine_tuner_model and refine_steps:
             x_ft = data[..., :-1]

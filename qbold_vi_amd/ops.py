@@ -69,6 +69,18 @@ def _laplace_cfg(what, max_iter, tol, lambda0, lambda_up, lambda_down):
     return _lib.LaplaceCfg(max_iter, lambda0, lambda_up, lambda_down, tol)
 
 
+def _adapt_cfg(what, rounds, K, shrink):
+    """The argument checks of adapt_posterior (raised before any launch): qbold_adapt_cfg."""
+    rounds, K, shrink = int(rounds), int(K), float(shrink)
+    if not 1 <= rounds <= _lib.QBOLD_ADAPT_MAX_ROUNDS:
+        raise ValueError(f"{what}: rounds must be in [1, {_lib.QBOLD_ADAPT_MAX_ROUNDS}]")
+    if K % 4 or not _lib.QBOLD_ADAPT_MIN_K <= K <= _lib.QBOLD_ADAPT_MAX_K:
+        raise ValueError(f"{what}: K must be a multiple of 4 in [{_lib.QBOLD_ADAPT_MIN_K}, {_lib.QBOLD_ADAPT_MAX_K}]")
+    if not 0.0 < shrink < math.inf:
+        raise ValueError(f"{what}: shrink must be positive and finite")
+    return _lib.AdaptCfg(rounds, K, shrink)
+
+
 def merge_ranges(pieces):
     """Sorted [offset, length] pieces with touching neighbours merged."""
     out = []
@@ -791,6 +803,41 @@ class Context:
                                                     _ptr(u0), C.byref(cfg), _ptr(q_out), _ptr(out), N, _stream()),
                    "qbold_laplace_posterior")
         return q_out, out
+
+    def adapt_posterior(self, x, mask, q, prior, sigma, rounds=6, K=64, shrink=4.0, z=None, seed=1, voxel0=0,
+                        want_rounds=False):
+        """Adaptive importance sampling per voxel by moment matching (qbold_adapt_posterior; Paananen et al. 2021):
+        `rounds` rounds of K draws from the current proposal (Philox stream 9 unless z [N, rounds K, 2] is given), each
+        weighted as log_evidence weights them; after every round but the last the proposal's mean and covariance move
+        to the weighted ones, shrunk by lambda = ESS / (ESS + shrink).  Starts from the heads q [N, 5] (the prior's own
+        row is a valid start) and returns the proposal of the round with the largest ESS, so a good q is not made
+        worse on the draws seen.  Voxels with mask <= 0 keep q's row and come back NaN in out.
+        Returns (q_out [N, 5] raw heads, for every entry that takes q; out [N, 2 rounds + 2] = (log p^_r, ESS_r) per
+        round, the returned round's index, flags: 1 a round skipped for non-finite weights, 2 a mean on the logit clip,
+        4 a spread head clamped) and, with want_rounds, q_rounds [N, rounds, 5], every round's proposal."""
+        cfg = _adapt_cfg("adapt_posterior", rounds, K, shrink)
+        rounds, K = cfg.rounds, cfg.K
+        x = _f32(x, "x", self.T)
+        N = x.numel() // self.T
+        q = _f32(q, "q", 5)
+        prior = _f32(prior, "prior", 5)
+        sigma = _f32(sigma, "sigma", self.T)
+        mask = _f32(mask, "mask") if mask is not None else None
+        z = _f32(z, "z", 2) if z is not None else None
+        for name, t, w in (("q", q, 5), ("prior", prior, 5), ("sigma", sigma, self.T), ("mask", mask, 1),
+                           ("z", z, rounds * K * 2)):
+            if t is not None and t.numel() != N * w:
+                raise ValueError(f"adapt_posterior: {name} does not match x ({N} voxels)" if name != "z" else
+                                 "adapt_posterior: z must be [N, rounds K, 2]")
+        q_out = torch.empty((N, 5), dtype=torch.float32, device=x.device)
+        out = torch.empty((N, 2 * rounds + 2), dtype=torch.float32, device=x.device)
+        q_rounds = torch.empty((N, rounds, 5), dtype=torch.float32, device=x.device) if want_rounds else None
+        if N > 0:   # empty tensors have no address to pass
+            _lib.check(self.lib.qbold_adapt_posterior(self.handle, _ptr(x), _ptr(mask), _ptr(q), _ptr(prior),
+                                                      _ptr(sigma), _ptr(z), C.byref(cfg), int(seed), int(voxel0),
+                                                      _ptr(q_out), _ptr(out), _ptr(q_rounds), N, _stream()),
+                       "qbold_adapt_posterior")
+        return (q_out, out, q_rounds) if want_rounds else (q_out, out)
 
     PPC_COLUMNS =("ppp", "dbar", "lppd", "p_waic", "elpd_waic", "max_abs_z")
 
