@@ -383,6 +383,52 @@ __device__ __forceinline__ void dense_first(const float* __restrict__ A,
     for (int m = 0; m < 4; ++m) out[m] = relu4(out[m]);
 }
 
+// clamp(v, lo, hi) as one v_med3_f32.  fminf(fmaxf(.)) on a loaded value costs a canonicalising v_max_f32 v, v, v in
+// front of the med3; the instruction itself needs none: with a quiet NaN it returns min3 = lo, which is clampf_'s
+// answer.  (A signalling NaN, which clampf_ would first quiet, is the one input the two forms may treat differently.)
+__device__ __forceinline__ float med3f_(float v, float lo, float hi) { return __builtin_amdgcn_fmed3f(v, lo, hi); }
+
+// normalise + dense_first's operand for the one-lane-per-voxel kernels (vi_fwd_kernel_vox), from only what lane (g, i)
+// feeds: the B fragment of k-slots 8g .. 8g + 7 of voxel row xrow[0 .. T).  The lane loads the spin-echo signal and
+// the 8-signal window of its row that starts at min(8g, T - 8) -- every address inside the row, the last voxel's row
+// ends the buffer -- and normalises those nine values with normalise's arithmetic, value for value.  Only group T / 8
+// can hold a partial window (T % 8 live slots, which sit at the window's end: one select each); k-slots at or beyond T
+// carry some other normalised signal of the same voxel, always finite (the clamp leaves [1e-2, 1e8], a NaN becomes
+// 1e-2), against first-layer weights that pack_kernel (wval) leaves at zero for in >= T: their products are zeros
+// added to accumulators that start from +0 or the bias, so every output is the bits of dense_first's.
+template <int T, int SE, bool BF = false>
+__device__ __forceinline__ void first_operand(const float* __restrict__ xrow, int lane, f16x8& hi, f16x8& lo) {
+    static_assert(T >= 8 && T <= 32 && SE >= 0 && SE < T, "one K = 32 step, windows of eight inside the row");
+    constexpr int R = T % 8, GP = T / 8;
+    const int g = lane >> 4;
+    const float* w = xrow + (8 * g < T - 8 ? 8 * g : T - 8);
+    float win[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) win[j] = w[j];
+    float se = xrow[SE];
+    // all loads leave before the first value is used: one memory latency per sub-tile, not the spin echo's and then
+    // the window's
+    asm volatile("" : "+v"(se), "+v"(win[0]), "+v"(win[1]), "+v"(win[2]), "+v"(win[3]), "+v"(win[4]), "+v"(win[5]),
+                      "+v"(win[6]), "+v"(win[7]));
+    const float inv_den = 1.0f / med3f_(se, 1e-2f, 1e8f);   // model.py:101, :106
+    float n[8], v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) n[j] = QB_LN2 * log2f_(med3f_(win[j], 1e-2f, 1e8f) * inv_den);  // model.py:108
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (j < R && g == GP) ? n[j < R ? j + 8 - R : j] : n[j];
+    split8<BF>(v, hi, lo);
+}
+
+// dense_first from a ready operand (first_operand)
+template <bool BF = false>
+__device__ __forceinline__ void dense_first_frag(const float* __restrict__ A, const float* __restrict__ bias,
+                                                 const f16x8& hi, const f16x8& lo, f32x4 (&out)[4], int lane) {
+    const f16x8 h[1] = {hi}, l[1] = {lo};
+    dense_f16x3<4, 1, BF>(A, bias, h, l, out, lane);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) out[m] = relu4(out[m]);
+}
+
 // The B fragments of relu(x) from those of x, on the packed halves: hi' = max(hi, 0), and lo' = lo where hi's sign
 // bit is clear, +0 where it is set.  Bit for bit split_act(relu4(x)): hi = f16(x) carries x's sign (x < 0 rounds to
 // a negative half or to -0, whose sign bit clears lo; v_pk_max_f16 orders -0 below +0 and returns +0, and
@@ -549,6 +595,83 @@ __device__ __forceinline__ void gather_head(const f32x4 (&acc)[HT], float (&o)[N
             }
         }
     }
+}
+
+// The head hand-over of the one-lane-per-voxel kernels: the head accumulators of sub-tile s are kept as they are in
+// register slot s (keep_head; s is wave-uniform, the caller branches on it), and after the fourth sub-tile
+// transpose_heads hands lane group g the rows of sub-tile g's voxels: slot s of group g held rows 4g + r of sub-tile
+// s, the 4 x 4 transpose of (slot, lane group) per register leaves rows 4s + r of sub-tile g there.  In place: the
+// half-wave bit of the group against the slots' upper bit (v_permlane32_swap on slots 0, 2 and 1, 3), then the row
+// bit against the lower one (v_permlane16_swap on slots 0, 1 and 2, 3).  head_row picks row k afterwards.
+// The slots are plain floats, 4 m + r for register r of head tile m.  keep_head_tile is ONE asm statement per head tile
+// that branches on the scalar s around four blocks of four moves, so that every slot keeps its register through the
+// rolled loop at the price of four v_mov_b32 per trip.  (Written as a C++ switch the branch is either turned into one
+// select per register and slot, or -- with the moves made opaque -- kept, with every slot copied around it.)  Inside an
+// asm string nothing is padded: FROM_MFMA (the bf16 encoder, whose head accumulators are raw MFMA results) opens with
+// the wait states between a matrix instruction's write and a vector read, and the string ends with the two states
+// v_permlane*_swap needs behind a vector write of its operands (transpose_heads may follow directly).
+#define QB_KEEP_HEAD_ASM(PAD)                                                                                          \
+    asm(PAD "s_cmp_lt_u32 %[s], 2\n\t"                                                                                  \
+        "s_cbranch_scc0 2f\n\t"                                                                                         \
+        "s_cmp_eq_u32 %[s], 0\n\t"                                                                                      \
+        "s_cbranch_scc0 1f\n\t"                                                                                         \
+        "v_mov_b32 %0, %[a0]\n\tv_mov_b32 %1, %[a1]\n\tv_mov_b32 %2, %[a2]\n\tv_mov_b32 %3, %[a3]\n\t"                  \
+        "s_branch 9f\n"                                                                                                \
+        "1:\n\t"                                                                                                       \
+        "v_mov_b32 %4, %[a0]\n\tv_mov_b32 %5, %[a1]\n\tv_mov_b32 %6, %[a2]\n\tv_mov_b32 %7, %[a3]\n\t"                  \
+        "s_branch 9f\n"                                                                                                \
+        "2:\n\t"                                                                                                       \
+        "s_cmp_eq_u32 %[s], 2\n\t"                                                                                      \
+        "s_cbranch_scc0 3f\n\t"                                                                                         \
+        "v_mov_b32 %8, %[a0]\n\tv_mov_b32 %9, %[a1]\n\tv_mov_b32 %10, %[a2]\n\tv_mov_b32 %11, %[a3]\n\t"                \
+        "s_branch 9f\n"                                                                                                \
+        "3:\n\t"                                                                                                       \
+        "v_mov_b32 %12, %[a0]\n\tv_mov_b32 %13, %[a1]\n\tv_mov_b32 %14, %[a2]\n\tv_mov_b32 %15, %[a3]\n"                 \
+        "9:\n\t"                                                                                                       \
+        "s_nop 1"                                                                                                      \
+        : "+v"(s0[0]), "+v"(s0[1]), "+v"(s0[2]), "+v"(s0[3]), "+v"(s1[0]), "+v"(s1[1]), "+v"(s1[2]), "+v"(s1[3]),      \
+          "+v"(s2[0]), "+v"(s2[1]), "+v"(s2[2]), "+v"(s2[3]), "+v"(s3[0]), "+v"(s3[1]), "+v"(s3[2]), "+v"(s3[3])       \
+        : [s] "s"(s), [a0] "v"(acc[0]), [a1] "v"(acc[1]), [a2] "v"(acc[2]), [a3] "v"(acc[3])                           \
+        : "scc")
+template <bool FROM_MFMA>
+__device__ __forceinline__ void keep_head_tile(int s, float (&s0)[4], float (&s1)[4], float (&s2)[4], float (&s3)[4],
+                                               const f32x4& acc) {
+    if constexpr (FROM_MFMA) {
+        QB_KEEP_HEAD_ASM("s_nop 15\n\ts_nop 3\n\t");
+    } else {
+        QB_KEEP_HEAD_ASM("");
+    }
+}
+#undef QB_KEEP_HEAD_ASM
+
+template <int HT>
+__device__ __forceinline__ void transpose_heads(float (&slot)[4][HT][4]) {
+#pragma unroll
+    for (int q = 0; q < 4 * HT; ++q) {
+        unsigned a[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) a[s] = __float_as_uint(slot[s][q >> 2][q & 3]);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {   // lanes 32..63 of slot s <-> lanes 0..31 of slot s + 2
+            const auto p = __builtin_amdgcn_permlane32_swap(a[s], a[s + 2], false, false);
+            a[s] = p[0];
+            a[s + 2] = p[1];
+        }
+#pragma unroll
+        for (int s = 0; s < 4; s += 2) {   // the odd 16-lane rows of slot s <-> the even rows of slot s + 1
+            const auto p = __builtin_amdgcn_permlane16_swap(a[s], a[s + 1], false, false);
+            a[s] = p[0];
+            a[s + 1] = p[1];
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) slot[s][q >> 2][q & 3] = __uint_as_float(a[s]);
+    }
+}
+
+// head row k of this lane's voxel after transpose_heads (gather_head's o[k])
+template <int HT>
+__device__ __forceinline__ float head_row(const float (&slot)[4][HT][4], int k) {
+    return slot[(k >> 2) & 3][k >> 4][k & 3];
 }
 
 }  // namespace qb

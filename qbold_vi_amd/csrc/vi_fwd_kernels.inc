@@ -6,6 +6,8 @@
 //     and the flag slot holding the larger of the two flags (copy_to_lds_fold, encoder_core.h: same footprint, the one
 //     barrier), and the blocks take their gate logits from relu(t)'s fragments (block_stream2<.., FOLD>).  Instantiated
 //     for the per-tau-table fast path only (GT), the path both layouts of the sampling phase share.
+// The four-lane kernels run normalise, dense_first and gather_head; the one-lane-per-voxel kernels run first_operand,
+// keep_head_tile and transpose_heads (encoder_core.h) to the same bits, and are tested against the four-lane ones.
 #if QB_VI_FOLD
 #define QB_VI_KERNEL(name) name##_fold
 #define QB_VI_GATE_FOLD_ARG const float* __restrict__ gate_fold,
@@ -133,9 +135,10 @@ __global__ __launch_bounds__(BLK) void QB_VI_KERNEL(vi_fwd_kernel)(
 }
 
 // The same tile loop with one lane per voxel through the sampling phase (header comment).  Per 64-voxel tile the encoder
-// phase runs four times, on the 16-voxel sub-tiles s = 0 .. 3, exactly as in vi_fwd_kernel; after sub-tile s the lanes
-// of group s keep their gathered head rows (a select per row: gather_head has just handed every group a copy), so that
-// lane (g, i) ends up with the heads of voxel 64 tile + 16 g + i = 64 tile + lane.  The sampling phase then runs once,
+// phase runs four times, on the 16-voxel sub-tiles s = 0 .. 3, with vi_fwd_kernel's arithmetic: the first layer's
+// operand comes from the nine signals the lane feeds it (first_operand), and the head accumulators of sub-tile s are
+// kept in register slot s; one transpose of (slot, lane group) behind the loop (transpose_heads) then leaves lane
+// (g, i) with the heads of voxel 64 tile + 16 g + i = 64 tile + lane.  The sampling phase then runs once,
 // voxel_mc_sums<.., 1> walking the four draw shares in vi_fwd_kernel's order (elbo_core.h): every per-voxel output is
 // the same bits whichever kernel took the voxel.  Built for the per-tau-table fast path only (GT in vi_fwd_kernel's
 // terms).  add_blocks: workgroups below it add their partial sums to what the slot holds (the four-lane launch over
@@ -159,6 +162,11 @@ __global__ __launch_bounds__(BLK) void QB_VI_KERNEL(vi_fwd_kernel_vox)(
     __syncthreads();
 
     constexpr int HT = (5 + T + 15) / 16;
+    // The head hand-over keeps the accumulators in slots and transposes once per tile (keep_head_tile, transpose_heads)
+    // everywhere but on the classic split-f16 image at two head tiles: there 32 slot registers, where o[] holds 29, on
+    // top of the classic block's peak do not fit the 168 registers of the 768-thread workgroup (12 bytes of scratch
+    // at T = 24, L = 2), and that kernel keeps gather_head and a select per row.
+    constexpr bool kSlots = HT == 1 || BF || QB_VI_FOLD;
     // Nothing per lane lives across the tile loop but the thread index: the encoder phases hold the finished sub-tiles'
     // head rows on top of their own peak, and every further loop-carried vector register would be spilled around them.
     // The wave index is read as a scalar (the tile counter and its bounds stay on the scalar unit), and the three
@@ -169,9 +177,15 @@ __global__ __launch_bounds__(BLK) void QB_VI_KERNEL(vi_fwd_kernel_vox)(
     const int64_t ntile = (N + 63) / 64;
     for (int64_t tile = (int64_t)blockIdx.x * kWaves + wave; tile < ntile;
          tile += (int64_t)gridDim.x * kWaves) {
-        float o[5 + T];
+        // slot s: the head accumulators of sub-tile s, each written in its own trip of the loop below (the empty asm
+        // defines it without an instruction); o: the head rows of this lane's voxel
+        float hs[4][HT][4], o[5 + T];
 #pragma unroll
-        for (int k = 0; k < 5 + T; ++k) o[k] = 0.0f;
+        for (int k = 0; k < 16 * HT; ++k) asm volatile("" : "=v"(hs[k / (4 * HT)][(k / 4) % HT][k % 4]));
+        if constexpr (!kSlots) {
+#pragma unroll
+            for (int k = 0; k < 5 + T; ++k) o[k] = 0.0f;
+        }
         // operand range guard: bit l = the voxel of lane l had an activation beyond the split's range in any of the four
         // lane groups that encoded it (a wave-uniform mask: it costs no vector register across the encoder phases)
         unsigned long long hot = 0;
@@ -181,18 +195,17 @@ __global__ __launch_bounds__(BLK) void QB_VI_KERNEL(vi_fwd_kernel_vox)(
             // encoder's LDS fragment addresses) is formed again for each sub-tile instead of living through all four
             int lane = lane0;
             asm volatile("" : "+v"(lane));
-            const int g = lane >> 4, i = lane & 15;
+            const int i = lane & 15;
             const int64_t ve = tile * 64 + 16 * s + i;
             const int64_t vc = ve < N ? ve : N - 1;
             float amax = lds_w[e.flag];
             __builtin_amdgcn_s_setprio(QB_PRIO_TILE_START);
-            float xv[T], nv[T];
-#pragma unroll
-            for (int t = 0; t < T; ++t) xv[t] = x[vc * T + t];
-            qb::normalise<T, SE>(c, xv, nv);
+            // the first layer's operand from the nine signals this lane feeds it (first_operand, encoder_core.h)
+            qb::f16x8 fhi, flo;
+            qb::first_operand<T, SE, BF>(x + vc * T, lane, fhi, flo);
             __builtin_amdgcn_s_setprio(2);
             f32x4 b[4];
-            qb::dense_first<T, BF>(lds_w + e.first_A, lds_w + e.first_b, nv, b, lane);
+            qb::dense_first_frag<BF>(lds_w + e.first_A, lds_w + e.first_b, fhi, flo, b, lane);
             if (!QB_ABLATE(c, 1) && qb_phase_fence()) {
                 qb::block_stream2<BF, true, QB_VI_FOLD>(lds_w + e.blk0, b, lane, &amax);
 #pragma unroll
@@ -200,10 +213,17 @@ __global__ __launch_bounds__(BLK) void QB_VI_KERNEL(vi_fwd_kernel_vox)(
             }
             f32x4 hd[HT];
             qb::dense_head<HT, BF>(lds_w + e.head_A, lds_w + e.head_b, b, hd, lane, &amax);
-            float os[5 + T];
-            qb::gather_head<5 + T, HT>(hd, os);
+            if constexpr (kSlots) {
+                // the head accumulators go to slot s as they are (s is wave-uniform: a scalar branch around four moves)
 #pragma unroll
-            for (int k = 0; k < 5 + T; ++k) o[k] = g == s ? os[k] : o[k];
+                for (int m = 0; m < HT; ++m) qb::keep_head_tile<BF>(s, hs[0][m], hs[1][m], hs[2][m], hs[3][m], hd[m]);
+            } else {
+                // gather_head hands every group a copy; the lanes of group s keep theirs, a select per row
+                float os[5 + T];
+                qb::gather_head<5 + T, HT>(hd, os);
+#pragma unroll
+                for (int k = 0; k < 5 + T; ++k) o[k] = (lane >> 4) == s ? os[k] : o[k];
+            }
             if constexpr (!BF) {
                 unsigned long long over = __ballot(qb::split_overflowed(amax));
                 over |= over >> 32;
@@ -212,6 +232,12 @@ __global__ __launch_bounds__(BLK) void QB_VI_KERNEL(vi_fwd_kernel_vox)(
             }
         }
         __builtin_amdgcn_s_setprio(0);
+        if constexpr (kSlots) {
+            // one transpose per tile: lane (g, i) takes the head rows of voxel 64 tile + 16 g + i
+            qb::transpose_heads<HT>(hs);
+#pragma unroll
+            for (int k = 0; k < 5 + T; ++k) o[k] = qb::head_row<HT>(hs, k);
+        }
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         const int64_t v = tile * 64 + lane;

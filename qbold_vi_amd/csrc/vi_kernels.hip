@@ -31,9 +31,16 @@
 // phases on 16-voxel sub-tiles, each exactly vi_fwd_kernel's, then ONE sampling phase in which a lane owns a voxel
 // and walks its four draw shares itself, in the four-lane order (voxel_mc_sums<.., 1>, elbo_core.h): the per-voxel
 // part runs once per voxel and every per-voxel output is the same bits.  The sub-tile loop stays rolled (unrolled it
-// is ~40 KB of code against a 64 KB instruction cache): after sub-tile s the lanes of group s keep the head rows
-// gather_head has just handed them, one select per row.  qbold_vi_fwd sends whole balanced rounds of 64-voxel tiles
-// (64 voxels on every wave of the device) to vi_fwd_kernel_vox and the remainder to vi_fwd_kernel.
+// is ~40 KB of code against a 64 KB instruction cache).  Two stretches of a sub-tile differ from vi_fwd_kernel's, in
+// what is issued and not in any value (encoder_core.h).  The front end: a lane loads and normalises the spin echo and
+// the eight signals of its voxel that it feeds the first layer (first_operand), not all T of them to pick eight, or
+// none, afterwards; the clamp is one v_med3_f32.  The head hand-over: the head accumulators of sub-tile s stay as they
+// are in register slot s (a scalar branch around four moves), and one in-place transpose of (slot, lane group) per
+// tile -- 16 v_permlane*_swap at T = 11 -- hands lane (g, i) the rows of voxel 16 g + i, where gather_head broadcast
+// every sub-tile's rows to all four groups and a select per row threw three copies away.  (The classic split-f16
+// image at T = 24, L = 2 keeps gather_head: the slots do not fit its registers, vi_fwd_kernels.inc.)  qbold_vi_fwd
+// sends whole balanced rounds of 64-voxel tiles (64 voxels on every wave of the device) to vi_fwd_kernel_vox and the
+// remainder to vi_fwd_kernel, which keeps normalise, dense_first and gather_head.
 //
 // The folded gate image (qbold_vi_fwd_folded; ops.vi_fwd's default).  A block's gate logits, Wg r + bg + gate_offset
 // with r = Wr2 relu(t) + br2, are affine in relu(t): (Wr2 Wg) relu(t) + (br2 Wg + bg + gate_offset).  The weights do
