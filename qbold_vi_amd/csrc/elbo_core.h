@@ -184,17 +184,40 @@ struct IsGtLds { static constexpr bool value = false; };
 template <int T, int SE>
 struct IsGtLds<GtLds<T, SE>> { static constexpr bool value = true; };
 
+// One evaluation in flight in the per-tau-table loop below: the table row and, unless the draw's operands are held in
+// registers (HELD), the tau's blood bracket from the LDS.
+template <bool HELD>
+struct GtStage {
+    float4 kk;
+    float bb;
+};
+template <>
+struct GtStage<true> {
+    float4 kk;
+};
+
 // The same with the per-tau OEF-indexed table (GtLds; qbold_dev.h): the host dispatches here only for protocols with
 // tau = 0 at the compile-time spin-echo index and a table built for them (qbold_ctx::gtab_ok).
 // sa, sb: the draw's two sigmoids (OEF = 0.8 sa + 0.04, DBV = 0.2 sb + 0.001, model.py:299-305).
-template <int T, int SE>
+// u: the draw's wave-uniform operands in vector registers (LikRegs, qbold_dev.h; the unpaired table only), or nothing:
+// the constants then come from c and the instruction stream and the blood brackets from the LDS, as they always did.
+template <int T, int SE, class U = NoDrawRegs>
 __device__ __forceinline__ float sample_sq_fast(const GtLds<T, SE>* L, const QbDev& c, const VoxelLik<T>& k,
-                                                float sa, float sb) {
+                                                float sa, float sb, const U& u = U()) {
     static_assert(SE >= 0 && gtab_segs(T) > 0, "built for compile-time spin-echo protocols");
+    static_assert(!U::kOn || !gtab_paired(T, SE), "held draw operands: built for the unpaired table");
     constexpr int NSEG = gtab_segs(T);
-    const FwdFast fv = fwd_fast_sig(c, sa, sb);
+    FwdFast fv;
+    float bb_se;
+    if constexpr (U::kOn) {
+        fv = fwd_fast_sig(u, sa, sb);
+        bb_se = u.bb[SE];
+    } else {
+        fv = fwd_fast_sig(c, sa, sb);
+        bb_se = L->blood_B[SE];
+    }
     float acc = 0.0f;
-    const float s_se = fmaf(fv.tissue_w, 1.0f, fv.blood_w * exp2f_(fv.ng * L->blood_B[SE]));   // F(0) = 0
+    const float s_se = fmaf(fv.tissue_w, 1.0f, fv.blood_w * exp2f_(fv.ng * bb_se));   // F(0) = 0
     const float inv_np = rcpf_(s_se + 1e-3f);
     const float lt = log2f_(fv.tissue_w * inv_np), lb = log2f_(fv.blood_w * inv_np);
     // one coordinate per draw: OEF in [0.04, 0.84] -> segment index and fraction shared by every tau.  The table's
@@ -255,20 +278,20 @@ __device__ __forceinline__ float sample_sq_fast(const GtLds<T, SE>* L, const QbD
         }
         return acc;
     } else {
-        struct Stage {
-            float4 kk;
-            float bb;
-        };
+        using Stage = GtStage<U::kOn>;   // with held operands a stage is the table row alone: the bracket is u.bb[t]
         auto issue = [&](int t) -> Stage {
             const int j = t > SE ? t - SE : SE - t;
             Stage st;
             st.kk = row[(j - 1) * NSEG];
-            st.bb = L->blood_B[t];
+            if constexpr (!U::kOn) st.bb = L->blood_B[t];
             return st;
         };
         auto finish = [&](int t, const Stage& st) {
             const float F = fmaf(fmaf(fmaf(st.kk.w, f, st.kk.z), f, st.kk.y), f, st.kk.x);
-            score(t, exp2f_(fmaf(fv.nd, F, lt)) + exp2f_(fmaf(fv.ng, st.bb, lb)));
+            float bb;
+            if constexpr (U::kOn) bb = u.bb[t];
+            else bb = st.bb;
+            score(t, exp2f_(fmaf(fv.nd, F, lt)) + exp2f_(fmaf(fv.ng, bb, lb)));
         };
         auto tau_of = [](int e) { return e < NA ? SE + 1 + e : e - NA; };
         constexpr int kDepth = T <= 16 ? QB_GT_DEPTH : QB_GT_DEPTH_LONG;
@@ -485,10 +508,12 @@ __device__ __forceinline__ float kl_draws_fast(const LogitMvn& q, const LogitMvn
 // Used by the one-lane-per-voxel path.  The four-lane path of voxel_mc_sums keeps its own copy of this loop in place:
 // called through this function every four-lane kernel comes out with the same instructions on other registers, and
 // those kernels are to stay what they were, listing included.
-template <int T, int SE, bool FAST, bool LITERAL, bool MIR, class LDS>
+// u: the draw's wave-uniform operands in vector registers (LikRegs; per-tau table only), or nothing.
+template <int T, int SE, bool FAST, bool LITERAL, bool MIR, class LDS, class U = NoDrawRegs>
 __device__ __forceinline__ float lik_draws(const LDS* L, const QbDev& c, const VoxelLik<T>& lik, const LogitMvn& q,
                                            int S, const float* __restrict__ zs, uint64_t seed, uint64_t vox, int part,
-                                           int& n_lik) {
+                                           int& n_lik, const U& u = U()) {
+    static_assert(!U::kOn || (FAST && IsGtLds<LDS>::value), "held draw operands: the per-tau-table fast path");
     float nll_sum = 0.0f;
     const int calls = S > 4 * part ? (S - 4 * part + 15) / 16 : 0;           // calls g = part + 4 k < ceil(S / 4)
     const int last = calls > 0 ? S - 4 * (part + 4 * (calls - 1)) : 0;      // draws of the last call: 1 .. 4
@@ -512,7 +537,9 @@ __device__ __forceinline__ float lik_draws(const LDS* L, const QbDev& c, const V
         float a, b, oef = 0.0f, dbv = 0.0f;
         reparam_logits(q, z0, z1, a, b);
         if constexpr (!(FAST && IsGtLds<LDS>::value)) forward_transform(a, b, oef, dbv);
-        if constexpr (FAST && IsGtLds<LDS>::value) {
+        if constexpr (U::kOn) {
+            nll_sum += sample_sq_fast<T, SE>(L, c, lik, sigmoidf_(a), sigmoidf_(b), u);
+        } else if constexpr (FAST && IsGtLds<LDS>::value) {
             static_assert(!IsGtLds<LDS>::value || MIR, "the per-tau table scores merged mirror pairs");
             nll_sum += sample_sq_fast<T, SE>(L, c, lik, sigmoidf_(a), sigmoidf_(b));
         } else if constexpr (FAST) {
@@ -542,7 +569,11 @@ __device__ __forceinline__ void share_sum(int p, float v, float& first, float& p
 // draws into a fresh accumulator, in the order and with the arithmetic of the lane of group p, each share closed by
 // the same fmaf, the KL's moment assembly replayed per share -- and adds them in voxel_sum's order: the same bits as
 // voxel_sum over four lanes.  The draws are addressed by (voxel, call, stream), so the stream does not move.
-template <int T, int SE, bool FAST, bool LITERAL, bool MIR = false, int LPV = QB_LANES_PER_VOXEL, class LDS>
+// DREGS (LPV = 1 on the per-tau table; the kernel says whether it has the registers): the likelihood draws read their
+// wave-uniform operands from vector registers (LikRegs, qbold_dev.h), formed once per call, that is once per tile, in
+// front of the four shares.  Same operations on the same values in the same order: the same bits.
+template <int T, int SE, bool FAST, bool LITERAL, bool MIR = false, int LPV = QB_LANES_PER_VOXEL, bool DREGS = false,
+          class LDS>
 __device__ __forceinline__ void voxel_mc_sums(const LDS* L, const QbDev& c,
                                               const VoxelLik<T>& lik, const LogitMvn& q,
                                               const float* __restrict__ prior_row, int S, int K,
@@ -551,6 +582,7 @@ __device__ __forceinline__ void voxel_mc_sums(const LDS* L, const QbDev& c,
                                               uint64_t vox, int part, float& nll_sum,
                                               float& kl_sum) {
     static_assert(LPV == QB_LANES_PER_VOXEL || (LPV == 1 && FAST), "one lane per voxel: built for the fast path");
+    static_assert(!DREGS || (LPV == 1 && IsGtLds<LDS>::value), "held draw operands: one lane per voxel on the per-tau table");
     nll_sum = 0.0f;
     kl_sum = 0.0f;
     int n_lik = 0, n_kl = 0;  // draws taken by this lane
@@ -561,9 +593,11 @@ __device__ __forceinline__ void voxel_mc_sums(const LDS* L, const QbDev& c,
     __builtin_amdgcn_s_setprio(QB_PRIO_LIK);
     if constexpr (LPV == 1) {
         float first = 0.0f, pair = 0.0f;
+        typename DrawRegsIf<DREGS, LikRegs<T, SE>>::type u;
+        u.form(L, c);
 #pragma unroll 1
         for (int p = 0; p < QB_LANES_PER_VOXEL; ++p) {
-            const float sq = lik_draws<T, SE, FAST, LITERAL, MIR>(L, c, lik, q, S, zs, seed, vox, p, n_lik);
+            const float sq = lik_draws<T, SE, FAST, LITERAL, MIR>(L, c, lik, q, S, zs, seed, vox, p, n_lik, u);
             share_sum(p, fmaf(0.5f, sq, (float)n_lik * lik.log_s_sum), first, pair);
         }
         nll_sum = first + pair;

@@ -212,6 +212,30 @@ __device__ __forceinline__ uint4 philox4x32(uint4 c, uint2 k) {
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) { return philox4x32<10>(c, k); }
 __device__ __forceinline__ uint4 philox4x32_7(uint4 c, uint2 k) { return philox4x32<7>(c, k); }
 
+// ---------------------------------------------------------------------------------------------
+// Wave-uniform operands of the likelihood draws held in vector registers (the one-lane-per-voxel fused kernels that
+// have the registers: vi_fwd_kernels.inc, kDrawRegs).  A constant of the context sits in an SGPR and a literal in the
+// instruction; where an instruction's encoding takes neither (a second constant, a literal in VOP3 on gfx950, an LDS
+// address) the compiler copies it to a VGPR with a v_mov_b32 per use, nine per likelihood draw.  vreg_ moves a value to
+// a VGPR ONCE and hides where it came from, so that it is neither rematerialised nor folded back: every use then reads
+// a vector register.  No value changes.  What pays is the moves and LDS reads that go; an SGPR source as such measured
+// no dearer inside the fused kernel than a VGPR one, unlike in the micro-benchmarks of MEASUREMENTS.md 4.4 (see 34).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float vreg_(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+// "nothing held": the default of every function that can take such registers; with it they compile to what they were
+struct NoDrawRegs {
+    static constexpr bool kOn = false;
+    template <class... A>
+    __device__ __forceinline__ void form(const A&...) {}
+};
+template <bool ON, class REGS>
+struct DrawRegsIf { using type = NoDrawRegs; };
+template <class REGS>
+struct DrawRegsIf<true, REGS> { using type = REGS; };
+
 #define QB_Z_MAX 4.8549f   // sqrt(-2 ln 2^-17) = 4.85487: the largest |z| the stream can produce
 
 // 1 + theta as a float in [1, 2): the word's top 23 bits as the mantissa
@@ -604,6 +628,42 @@ __device__ __forceinline__ FwdFast fwd_fast_sig(const QbDev& c, float sa, float 
     v.blood_w = fmaf(sb, c.bv_a, c.bv_b);
     const float oef = fmaf(sa, QB_OEF_RANGE, QB_MIN_OEF);
     v.ng = c.ngk_l2e * (oef * oef);
+    return v;
+}
+// The likelihood draw's wave-uniform operands in vector registers (vreg_ above): the blood brackets of the taus a draw
+// evaluates and fwd_fast_sig's constants (18 registers at T = 11, 26 at T = 24).  The literals of the draw's front
+// (Box-Muller's u1, the sigmoids' -log2(e), the table coordinate's scale) stay literals: four more registers put
+// vi_fwd_kernel_vox_fold<11,2,2,false,1024> into scratch (MEASUREMENTS.md 34).
+// Formed once per tile behind the encoder phases; the per-tau-table likelihood loop (sample_sq_fast, elbo_core.h)
+// then reads no SGPR, no literal it would have to move, and no LDS word but its table rows.
+template <int T, int SE>
+struct LikRegs {
+    static constexpr bool kOn = true;
+    float bb[T];   // blood_B of the evaluated taus: SE .. T - 1 and the taus below SE without a partner on the grid
+    float nd_a, nd_b, tw_a, tw_b, bv_a, bv_b, ngk_l2e, oef_range, oef_min;
+    __device__ __forceinline__ void form(const GtLds<T, SE>* L, const QbDev& c) {
+        constexpr int NB = (2 * SE - (T - 1)) > 0 ? 2 * SE - (T - 1) : 0;
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+            if (t >= SE || t < NB) bb[t] = vreg_(L->blood_B[t]);
+        nd_a = vreg_(c.nd_a); nd_b = vreg_(c.nd_b);
+        tw_a = vreg_(c.tw_a); tw_b = vreg_(c.tw_b);
+        bv_a = vreg_(c.bv_a); bv_b = vreg_(c.bv_b);
+        ngk_l2e = vreg_(c.ngk_l2e);
+        oef_range = vreg_(QB_OEF_RANGE);
+        oef_min = vreg_(QB_MIN_OEF);
+    }
+};
+// fwd_fast_sig on those registers: the same five operations on the same values
+template <int T, int SE>
+__device__ __forceinline__ FwdFast fwd_fast_sig(const LikRegs<T, SE>& u, float sa, float sb) {
+    FwdFast v;
+    v.ua = v.ub = 0.0f;
+    v.nd = fmaf(sb, u.nd_a, u.nd_b);
+    v.tissue_w = fmaf(sb, u.tw_a, u.tw_b);
+    v.blood_w = fmaf(sb, u.bv_a, u.bv_b);
+    const float oef = fmaf(sa, u.oef_range, u.oef_min);
+    v.ng = u.ngk_l2e * (oef * oef);
     return v;
 }
 __device__ __forceinline__ float fwd_signal_fast(const FwdLds* L, const QbDev& c, const FwdFast& v,

@@ -167,6 +167,11 @@ __global__ __launch_bounds__(BLK) void QB_VI_KERNEL(vi_fwd_kernel_vox)(
     // top of the classic block's peak do not fit the 168 registers of the 768-thread workgroup (12 bytes of scratch
     // at T = 24, L = 2), and that kernel keeps gather_head and a select per row.
     constexpr bool kSlots = HT == 1 || BF || QB_VI_FOLD;
+    // The likelihood draws read their wave-uniform operands from vector registers (voxel_mc_sums<.., DREGS>, elbo_core.h:
+    // 18 registers at T = 11, 26 at T = 24) in every instance that keeps its register budget without scratch with them.
+    // Eleven of the twelve do (MEASUREMENTS.md 34 lists them); the classic split-f16 image at T = 11, L = 2 takes 12
+    // bytes of scratch and keeps SGPR and literal operands.
+    constexpr bool kDrawRegs = BF || QB_VI_FOLD || !(T == 11 && NL == 2);
     // Nothing per lane lives across the tile loop but the thread index: the encoder phases hold the finished sub-tiles'
     // head rows on top of their own peak, and every further loop-carried vector register would be spilled around them.
     // The wave index is read as a scalar (the tile counter and its bounds stay on the scalar unit), and the three
@@ -261,8 +266,8 @@ __global__ __launch_bounds__(BLK) void QB_VI_KERNEL(vi_fwd_kernel_vox)(
             }
             if (!BF && ((hot >> lane) & 1)) lik.log_s_sum = __builtin_nanf("");
             float nll_sum, kl_sum;
-            qb::voxel_mc_sums<T, SE, true, false, true, 1>(L, c, lik, qm, prior + v * 5, S, K, nullptr, nullptr, seed,
-                                                           (uint64_t)(voxel0 + v), 0, nll_sum, kl_sum);
+            qb::voxel_mc_sums<T, SE, true, false, true, 1, kDrawRegs>(L, c, lik, qm, prior + v * 5, S, K, nullptr, nullptr,
+                                                                      seed, (uint64_t)(voxel0 + v), 0, nll_sum, kl_sum);
             int Sd = S, Kd = K;   // opaque: (float)S and (float)K are formed here, not carried through the tile loop
             asm volatile("" : "+s"(Sd), "+s"(Kd));
             const float nll = nll_sum / (float)Sd;

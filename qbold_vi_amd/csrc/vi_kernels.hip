@@ -40,7 +40,10 @@
 // every sub-tile's rows to all four groups and a select per row threw three copies away.  (The classic split-f16
 // image at T = 24, L = 2 keeps gather_head: the slots do not fit its registers, vi_fwd_kernels.inc.)  qbold_vi_fwd
 // sends whole balanced rounds of 64-voxel tiles (64 voxels on every wave of the device) to vi_fwd_kernel_vox and the
-// remainder to vi_fwd_kernel, which keeps normalise, dense_first and gather_head.
+// remainder to vi_fwd_kernel, which keeps normalise, dense_first and gather_head.  Where the registers allow (every
+// instance but the classic split-f16 image at T = 11, L = 2) the likelihood draws of vi_fwd_kernel_vox read their
+// wave-uniform operands -- the blood brackets, fwd_fast_sig's constants -- from vector registers filled once per tile
+// (LikRegs, qbold_dev.h).
 //
 // The folded gate image (qbold_vi_fwd_folded; ops.vi_fwd's default).  A block's gate logits, Wg r + bg + gate_offset
 // with r = Wr2 relu(t) + br2, are affine in relu(t): (Wr2 Wg) relu(t) + (br2 Wg + bg + gate_offset).  The weights do
