@@ -713,6 +713,73 @@ int qbold_adapt_posterior(const qbold_ctx* ctx, const float* x, const float* mas
                           int64_t voxel0, float* q_out, float* out, float* q_rounds /* nullable */, int64_t N,
                           void* stream);
 
+/* Fisher information of the likelihood the library fits with, at given points, and the Cramer-Rao bounds that follow
+ * (this package's addition): how well a tau protocol can determine OEF and DBV in a voxel at all, apart from any fit.
+ *   A point is theta = (OEF, DBV) with logits (a, b) through forward_transform.  yhat_t(theta) = s_t / (mean of s over
+ *   the normalisation window + 1e-3) is the prediction the likelihood scores, sigma_t its per-tau standard deviation,
+ *   w_t >= 0 the per-tau weights: the number of averages of tau t, so that the variance is sigma_t^2 / w_t; w_t = 0
+ *   drops the tau.  Rows j_t = (d yhat_t / da, d yhat_t / db) / sigma_t, formed exactly as qbold_laplace_posterior
+ *   forms its Jacobian rows (the table's own F without Simpson node 0's slope, the window's one or three images first).
+ *     I(theta; w) = sum_t w_t j_t j_t^T      the data information, 2 x 2 on the logit plane
+ *     Lambda = L_p^-T L_p^-1                 the prior precision, (mu_p, L_p) = make_mvn of prior[5]
+ *     A = I + Lambda, Sigma = A^-1           the Bayesian information and its bound
+ *   This is the information of independent noise sigma_t on the NORMALISED data: the normaliser's own noise is ignored,
+ *   as the likelihood ignores it.  Under one-image normalisation the spin-echo row is therefore ~ 0 although that image
+ *   must be acquired; the library does not account for that (scripts/design_protocol.py --require-se does).
+ *   theta [N][2]; sigma [sigma_rows][T], sigma_rows = N (per voxel) or 1 (one row shared by all voxels); weights [T] or
+ *   NULL = all ones (the same bits); prior [N][5] or NULL; mask [N] or NULL = ones.
+ *   out [N][QBOLD_FISHER_OUT]:
+ *      0-2  I_aa, I_ab, I_bb
+ *      3    kappa = (I_aa I_bb + I_ab^2) / det I, the conditioning of the data information
+ *      4    log det I
+ *      5-8  the data-only Cramer-Rao bound I^-1: sd of OEF, DBV, R2' = dw_coef OEF DBV (delta method through the
+ *           transforms' slopes, as qbold_laplace_posterior's columns 8-10), and the OEF-DBV correlation of I^-1
+ *      9-12 the same four from Sigma = (I + Lambda)^-1; NaN when prior is NULL
+ *      13   log det A; NaN when prior is NULL
+ *      14   flags, as a float: bit 0 = the data information is singular to float32, det I <= 2^-20 (I_aa I_bb + I_ab^2):
+ *           column 3 is then +inf and columns 4-8 are -inf, +inf, +inf, +inf, NaN (columns 9-13 stand, A is positive
+ *           definite through the prior); bit 1 = theta outside the transforms' open ranges (0.04, 0.84) x (0.001,
+ *           0.201), or NaN: columns 0-13 are NaN and this column is 2
+ *   Voxels with mask <= 0 (or NaN) get a NaN row, flags included.  No random stream, no atomics, no sums, no workspace:
+ *   a voxel's row is the same bits in any batch at any position.  One run-time-T kernel serves every 1 <= T <= 64.
+ * Configurations: qbold_laplace_posterior's; QBOLD_ERR_UNSUPPORTED otherwise.  QBOLD_ERR_INVALID for a NULL out (theta,
+ * sigma when N > 0), sigma_rows not in {1, N}, N < 0 and a negative or non-finite weight; these are checked first.
+ * The weights are checked on the host: when given, this entry reads T floats back and WAITS for `stream` (the one
+ * exception to the rule at the top). */
+#define QBOLD_FISHER_OUT 15
+int qbold_fisher_information(const qbold_ctx* ctx, const float* theta, const float* sigma, int64_t sigma_rows,
+                             const float* weights /* nullable */, const float* prior /* nullable */,
+                             const float* mask /* nullable */, float* out, int64_t N, void* stream);
+
+/* Scores of B designs of the tau protocol at once (this package's addition): a design is a row of per-tau weights w_b
+ * on the context's tau grid, as above.  For every design the masked sums over the voxels of
+ *      0    log det A_b, A_b = I(theta; w_b) + Lambda: summed over draws theta of a prior this is the Bayesian
+ *           D-criterion E_theta log det(I + Lambda) (Chaloner & Verdinelli 1995)
+ *      1-3  the variances of OEF, DBV and R2' from Sigma_b = A_b^-1 by the delta method (the squares of
+ *           qbold_fisher_information's columns 9-11)
+ *      4    sum of the mask weights
+ *   scores: DEVICE double [B][QBOLD_DESIGN_OUT] = sum over voxels with m > 0 of m times the value (column 4: of m).
+ *   per_voxel [B][N][4] or NULL (16-byte aligned): the four values per design and voxel, unweighted; NaN where
+ *     mask <= 0 (or NaN).  A voxel's values are qbold_fisher_information's arithmetic to the bit (column 13; the
+ *     variances before their square root).
+ *   weights [B][T]: finite and >= 0 (NOT checked here: the buffer is the caller's on the device; a negative weight can
+ *     make A indefinite and a NaN weight makes that design's scores NaN).  prior [N][5] is REQUIRED: A is then positive
+ *     definite whatever the design, no design or voxel is dropped and no threshold decides anything.  A theta outside
+ *     the transforms' open ranges makes its values, and every sum it enters, NaN.
+ *   workspace: qbold_design_workspace_bytes(ctx, N, B) bytes, 8-byte aligned, not kept between calls; a caller with
+ *     less memory scores the designs in several calls (a design's sums do not depend on its batch).
+ *   Sums: partials belong to fixed 256-voxel tiles (four 64-voxel wave tiles, each added in voxel order, in double)
+ *   and are added in tile order: the same bits run to run, at any launch grid, in any slot of any batch of designs.
+ *   theta, sigma, sigma_rows, mask, the supported configurations and QBOLD_ERR_UNSUPPORTED as above.
+ * QBOLD_ERR_INVALID for N < 0, B < 0, a NULL required buffer (scores, workspace when B > 0; theta, sigma, weights,
+ * prior when N > 0 and B > 0), sigma_rows not in {1, N}, a misaligned workspace or per_voxel.  N = 0 returns zero sums,
+ * B = 0 writes nothing. */
+#define QBOLD_DESIGN_OUT 5
+int64_t qbold_design_workspace_bytes(const qbold_ctx* ctx, int64_t N, int64_t B);
+int qbold_design_scores(const qbold_ctx* ctx, const float* theta, const float* sigma, int64_t sigma_rows,
+                        const float* weights, const float* prior, const float* mask /* nullable */, double* scores,
+                        float* per_voxel /* nullable */, void* workspace, int64_t N, int64_t B, void* stream);
+
 /* Posterior predictive checks of the fine-tuning model per voxel (this package's addition; the reference has no
  * counterpart): Gelman, Meng & Stern 1996 for the p-value, Watanabe 2010 / Vehtari, Gelman & Gabry 2017 for lppd and
  * WAIC.  theta_l, l = 0 .. L-1: the reparameterised draws of q (heads [N][5], the use_mvg = True family), from explicit

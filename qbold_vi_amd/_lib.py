@@ -26,6 +26,8 @@ QBOLD_LAPLACE_OUT = 15   # columns of qbold_laplace_posterior's out
 QBOLD_ADAPT_MAX_ROUNDS = 16   # qbold_adapt_posterior
 QBOLD_ADAPT_MIN_K = 8
 QBOLD_ADAPT_MAX_K = 1024
+QBOLD_FISHER_OUT = 15    # columns of qbold_fisher_information's out
+QBOLD_DESIGN_OUT = 5     # columns of qbold_design_scores' scores
 
 
 class QboldError(RuntimeError):
@@ -159,6 +161,9 @@ SIGNATURES = {
     "qbold_laplace_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(LaplaceCfg), _P, _P, _I64, _P]),
     "qbold_adapt_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(AdaptCfg), _U64, _I64, _P, _P, _P, _I64,
                                         _P]),
+    "qbold_fisher_information": (C.c_int, [_P, _P, _P, _I64, _P, _P, _P, _P, _I64, _P]),
+    "qbold_design_workspace_bytes": (_I64, [_P, _I64, _I64]),
+    "qbold_design_scores": (C.c_int, [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _P]),
     "qbold_posterior_predictive": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _I64, _P]),
     "qbold_loo_workspace_bytes": (_I64, [_P, C.c_int, _I64]),
     "qbold_loo": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _P, _P, _I64, _P]),

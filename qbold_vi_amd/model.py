@@ -476,6 +476,34 @@ class FineTuner:
                     r2p_sd=col(10), log_evidence=col(11), chi2=col(12), iterations=col(13),
                     converged=(live & ((flags & 1) == 0)).reshape(lead), on_clip=bit(1), clamped=bit(2))
 
+    def identifiability(self, data, mask, prior, q=None, no_samples=200):
+        """How well the protocol can determine OEF and DBV in each voxel at all (Context.fisher_information): the Fisher
+        information of the fitted likelihood -- independent noise sigma on the normalised data, the normaliser's own
+        noise ignored -- at the posterior means of the heads q [..., 5] (None: the encoder's), with the sigma refine()
+        takes.  A wide posterior beside a wide bound is the protocol's doing, beside a narrow one the encoder's.
+        Shaped like the data's spatial dims:
+          oef_crlb, dbv_crlb, r2p_crlb (data-only Cramer-Rao sds), corr, kappa (correlation and conditioning of the data
+            information: the OEF . DBV ridge), singular (bool)
+          oef_bound, dbv_bound, r2p_bound (sds from (I + Lambda)^-1, Lambda the prior's precision)
+          oef_ratio, dbv_ratio, r2p_ratio: the posterior sd (calculate_means(return_stds=True), `no_samples` draws) over
+            its Bayesian bound
+        Voxels outside the mask are NaN."""
+        tr = self._trainer
+        self._check_mvn_family("identifiability")
+        T = data.shape[-1]
+        m = None if mask is None else mask.reshape(-1)
+        p5 = _flat(prior, prior.shape[-1]).contiguous()
+        q, sg = self._heads_and_sigma(data, q)
+        means, var = tr.calculate_means(q, None, include_r2p=True, return_stds=True, no_samples=no_samples)
+        f = tr._ctx.fisher_information(means[:, :2].contiguous(), sg.reshape(-1, T), None, p5, m)
+        lead = data.shape[:-1]
+        out = {k: f[k].reshape(lead) for k in ("oef_crlb", "dbv_crlb", "r2p_crlb", "corr", "kappa", "singular",
+                                                "oef_bound", "dbv_bound", "r2p_bound")}
+        sd = torch.sqrt(var)
+        for i, k in enumerate(("oef", "dbv", "r2p")):
+            out[k + "_ratio"] = (sd[:, i] / f[k + "_bound"]).reshape(lead)
+        return out
+
     def adapt(self, data, mask, prior, q=None, rounds=6, no_samples=64, shrink=4.0, seed=1, voxel0=0):
         """Adaptive importance sampling per voxel by moment matching (Context.adapt_posterior; Paananen et al. 2021):
         `rounds` rounds of `no_samples` draws, after each of which the proposal moves to the importance-weighted mean
@@ -961,7 +989,7 @@ class EncoderTrainer:
     def save_predictions(self, model, data, filename, transform_directory=None, use_first_op=True,
                          fine_tuner_model=None, priors=None, iw_samples=None, refine_steps=None,
                          posterior_grid=None, ppc_samples=None, refine_smoothness_weight=0.0, psis=False,
-                         loo_samples=None, laplace=False, adapt_rounds=None):
+                         loo_samples=None, laplace=False, adapt_rounds=None, identifiability=False):
         """model.py:772-887: write `<filename>_{oef,dbv,r2p,logstds}.nii.gz` (posterior means of
         OEF / DBV / R2' over 200 draws and their variances) and, with a fine tuner,
         `_likelihood` (per-voxel NLL averaged over 100 stochastic passes), `_kl` (100-draw KL to
@@ -1003,6 +1031,10 @@ class EncoderTrainer:
         `_dbv_adapt`, `_r2p_adapt` (calculate_means of the adapted heads) and `_ess_adapt` (the returned round's ESS
         over its draws, in (0, 1]), zero outside the mask; with iw_samples (and psis) the importance maps above are
         taken under the adapted heads, so `_khat` is theirs.  These maps join the returned dict.
+        identifiability = True (with a fine tuner; this package's addition, default off): what the protocol can
+        determine at the encoder's posterior means (FineTuner.identifiability) as `_oef_crlb`, `_dbv_crlb`, `_r2p_crlb`
+        (data-only Cramer-Rao sds), `_crlbcorr` and `_crlbkappa` (correlation and conditioning of the data information),
+        zero outside the mask; these maps join the returned dict.
         data [subj, X, Y, Z, T+1] with the mask last; each map is stored as [X, Y, Z, subj*C].
         `transform_directory/example.nii.gz`, when present, donates its header (:794-797); the
         FSL `applywarp`/`fslmerge` MNI step (:850-879) is preprocessing outside this package and
@@ -1013,6 +1045,8 @@ class EncoderTrainer:
             raise ValueError("save_predictions(laplace=True) needs a fine tuner (its sigma and the prior maps)")
         if adapt_rounds and not fine_tuner_model:
             raise ValueError("save_predictions(adapt_rounds=R) needs a fine tuner (its sigma and the prior maps)")
+        if identifiability and not fine_tuner_model:
+            raise ValueError("save_predictions(identifiability=True) needs a fine tuner (its sigma and the prior maps)")
         data = torch.as_tensor(data, dtype=torch.float32, device=self._ctx.device)
         T = self._ctx.T
         mask = data[..., -1:]
@@ -1169,6 +1203,17 @@ class EncoderTrainer:
             for k, v in lap_maps.items():
                 save_im_data(v, filename + '_' + k)
             iw_maps = dict(iw_maps or {}, **lap_maps)
+
+        if fine_tuner_model and identifiability:
+            idf = fine_tuner_model.identifiability(data[..., :-1], mask,
+                                                   torch.as_tensor(priors, device=data.device)[..., :self._nq])
+            live = mask[..., 0] > 0
+            id_maps = {k: torch.where(live, idf[src], torch.zeros_like(idf[src]))[..., None] for k, src in
+                       (("oef_crlb", "oef_crlb"), ("dbv_crlb", "dbv_crlb"), ("r2p_crlb", "r2p_crlb"),
+                        ("crlbcorr", "corr"), ("crlbkappa", "kappa"))}
+            for k, v in id_maps.items():
+                save_im_data(v, filename + '_' + k)
+            iw_maps = dict(iw_maps or {}, **id_maps)
 
         save_im_data(means[..., 0:1], filename + '_oef')
         save_im_data(means[..., 1:2], filename + '_dbv')

@@ -839,6 +839,84 @@ class Context:
                        "qbold_adapt_posterior")
         return (q_out, out, q_rounds) if want_rounds else (q_out, out)
 
+    FISHER_COLUMNS = ("i_aa", "i_ab", "i_bb", "kappa", "log_det", "oef_crlb", "dbv_crlb", "r2p_crlb", "corr",
+                      "oef_bound", "dbv_bound", "r2p_bound", "corr_bound", "log_det_bayes", "flags")
+    DESIGN_COLUMNS = ("log_det", "oef_var", "dbv_var", "r2p_var", "mask_sum")
+
+    def _design_inputs(self, what, theta, sigma, prior, mask):
+        """(theta [N, 2], sigma, sigma_rows, prior or None, mask or None, N) of the information entries."""
+        for name, t in (("theta", theta), ("sigma", sigma), ("prior", prior), ("mask", mask)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+                raise ValueError(f"{what}: {name} must be a cuda (ROCm) tensor; there is no CPU fallback")
+        theta = _f32(theta, "theta", 2)
+        N = theta.numel() // 2
+        sigma = _f32(sigma, "sigma", self.T)
+        rows = sigma.numel() // self.T
+        if rows not in (1, N):
+            raise ValueError(f"{what}: sigma must be [N, T] or one row [T] shared by all voxels")
+        prior = _f32(prior, "prior", 5) if prior is not None else None
+        mask = _f32(mask, "mask") if mask is not None else None
+        for name, t, w in (("prior", prior, 5), ("mask", mask, 1)):
+            if t is not None and t.numel() != N * w:
+                raise ValueError(f"{what}: {name} does not match theta ({N} voxels)")
+        return theta, sigma, rows, prior, mask, N
+
+    def fisher_information(self, theta, sigma, weights=None, prior=None, mask=None):
+        """Fisher information of the likelihood the library fits with at the points theta [N, 2] = (OEF, DBV), and
+        the Cramer-Rao bounds from it (qbold_fisher_information): independent noise sigma on the NORMALISED data, the
+        normaliser's own noise ignored.  sigma [N, T] or one shared row [T]; weights [T] >= 0 = averages per tau (None:
+        ones); with prior [N, 5] also the Bayesian bounds from (I + Lambda)^-1.  Voxels with mask <= 0 come back NaN.
+        Returns a dict of the columns of FISHER_COLUMNS ([N] each; `singular` and `out_of_range` as bool from the
+        flags) plus "out" [N, 15]."""
+        theta, sigma, rows, prior, mask, N = self._design_inputs("fisher_information", theta, sigma, prior, mask)
+        if weights is not None:
+            if not (isinstance(weights, torch.Tensor) and weights.is_cuda):
+                raise ValueError("fisher_information: weights must be a cuda (ROCm) tensor; there is no CPU fallback")
+            weights = _f32(weights, "weights")
+            if weights.numel() != self.T:
+                raise ValueError(f"fisher_information: weights must hold T = {self.T} values")
+        out = torch.empty((N, _lib.QBOLD_FISHER_OUT), dtype=torch.float32, device=theta.device)
+        if N > 0:   # empty tensors have no address to pass
+            _lib.check(self.lib.qbold_fisher_information(self.handle, _ptr(theta), _ptr(sigma), rows, _ptr(weights),
+                                                         _ptr(prior), _ptr(mask), _ptr(out), N, _stream()),
+                       "qbold_fisher_information")
+        d = {k: out[:, i] for i, k in enumerate(self.FISHER_COLUMNS)}
+        flags = torch.nan_to_num(out[:, 14]).int()
+        d["singular"], d["out_of_range"], d["out"] = (flags & 1) != 0, (flags & 2) != 0, out
+        return d
+
+    def design_scores(self, theta, sigma, weights, prior, mask=None, want_per_voxel=False, workspace_bytes=1 << 28):
+        """Scores of B designs of the tau protocol at once (qbold_design_scores): weights [B, T] >= 0, a row = the
+        number of averages per tau; theta [N, 2] points (draws of a prior, say), sigma [N, T] or one shared row,
+        prior [N, 5] (required).  Returns scores, a float64 device tensor [B, 5] with the columns of DESIGN_COLUMNS:
+        the masked sums over the voxels of log det(I + Lambda) (the Bayesian D-criterion), of the delta-method
+        variances of OEF, DBV and R2', and of the mask; with want_per_voxel also per_voxel [B, N, 4].  The designs are
+        scored in chunks whose workspace fits `workspace_bytes`; a design's sums do not depend on the chunking."""
+        theta, sigma, rows, prior, mask, N = self._design_inputs("design_scores", theta, sigma, prior, mask)
+        if prior is None:
+            raise ValueError("design_scores: the prior is required (it keeps I + Lambda positive definite)")
+        if not (isinstance(weights, torch.Tensor) and weights.is_cuda):
+            raise ValueError("design_scores: weights must be a cuda (ROCm) tensor; there is no CPU fallback")
+        weights = _f32(weights, "weights", self.T).reshape(-1, self.T)
+        B = weights.shape[0]
+        if B and not bool((torch.isfinite(weights) & (weights >= 0)).all()):
+            raise ValueError("design_scores: weights must be finite and >= 0")
+        scores = torch.zeros((B, _lib.QBOLD_DESIGN_OUT), dtype=torch.float64, device=theta.device)
+        per_voxel = torch.empty((B, N, 4), dtype=torch.float32, device=theta.device) if want_per_voxel else None
+        if B:
+            per_design = int(self.lib.qbold_design_workspace_bytes(self.handle, N, 1))
+            chunk = max(1, min(B, int(workspace_bytes) // max(per_design, 1)))
+            ws = torch.empty(int(self.lib.qbold_design_workspace_bytes(self.handle, N, chunk)) // 8,
+                             dtype=torch.float64, device=theta.device)
+            for b0 in range(0, B, chunk):
+                nb = min(chunk, B - b0)
+                _lib.check(self.lib.qbold_design_scores(
+                    self.handle, _ptr(theta) if N else None, _ptr(sigma) if N else None, rows if N else 0,
+                    _ptr(weights[b0:b0 + nb]), _ptr(prior) if N else None, _ptr(mask) if N and mask is not None else None,
+                    _ptr(scores[b0:b0 + nb]), _ptr(per_voxel[b0:b0 + nb]) if want_per_voxel and N else None,
+                    _ptr(ws), N, nb, _stream()), "qbold_design_scores")
+        return (scores, per_voxel) if want_per_voxel else scores
+
     PPC_COLUMNS =("ppp", "dbar", "lppd", "p_waic", "elpd_waic", "max_abs_z")
 
     def posterior_predictive(self, x, mask, q, sigma, L=256, z=None, seed=1, voxel0=0, want_curves=False):
