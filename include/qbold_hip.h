@@ -497,6 +497,47 @@ int qbold_log_evidence_draws(const qbold_ctx* ctx, const float* x, const float* 
 int qbold_psis(const qbold_ctx* ctx, const float* log_w, const float* theta, int C, const float* mask, int K,
                float* out, float* means, float* weights, int64_t N, void* stream);
 
+/* Summaries of N independent rows of K weighted draws: moments, weighted quantiles, the highest-density interval and
+ * correlations (this package's addition; like qbold_psis, nothing of the qBOLD model enters).
+ *   log_w [N][K], or NULL for equal weights (the intervals of q's own draws): -inf is a zero weight; a NaN, a +inf or
+ *     no finite value in a row makes every output of the row NaN (qbold_psis's rule).  Raw log_w and qbold_psis'
+ *     normalised `weights` are both valid inputs.
+ *   theta [N][K][C], 1 <= C <= QBOLD_SUMMARY_MAX_C: a NaN in a column makes that column's outputs NaN; the other
+ *     columns and row_out are unaffected.
+ *   mask [N] or NULL (= ones): rows with mask <= 0 (or NaN) are not read; their outputs are NaN.
+ *   K in [QBOLD_SUMMARY_MIN_K, QBOLD_SUMMARY_MAX_K];  P in [0, QBOLD_SUMMARY_MAX_P] levels probs_host[P], read from the
+ *     host, each strictly inside (0, 1);  hpd_mass strictly inside (0, 1).
+ * Definitions, per row and column:
+ *   w~_k = exp(lw_k - max) / sum_j exp(lw_j - max).
+ *   mean = sum w~ theta.
+ *   sd = sqrt(sum w~ (theta - mean)^2), computed in two passes with no Bessel correction.
+ *   Sort the column ascending.  Equal values are ordered by ascending draw.  W_r is the inclusive cumulative sum of w~
+ *   in that order.
+ *   Quantile at level p = theta_(r*), with r* = min{r : W_r >= p}; r* is clamped to K - 1.  This is the inverse
+ *   weighted ECDF (numpy's `inverted_cdf`).  It does not interpolate, so the result is always one of the draws.
+ *   HPD = the shortest [theta_(a), theta_(b)] with W_b - W_{a-1} >= hpd_mass.  For each a, b(a) is the smallest feasible
+ *   b.  Width ties go to the smallest a.  An a with no feasible b is skipped.
+ *   row_out [N][2] = (ESS = 1 / sum w~^2, max_k w~_k).
+ *   corr [N][C (C - 1) / 2], or NULL.  It holds the weighted Pearson correlations in the pair order (0,1), (0,2), ...,
+ *   (C-2,C-1).  An entry is NaN where an sd is 0.
+ *   stats [N][C][4] = (mean, sd, hpd_lo, hpd_hi).
+ *   quant [N][C][P], or NULL when P = 0.
+ * The kernel works in float32: W_r is within (K + 32) 2^-24 of its exact value, so a quantile lies between the exact
+ * rule's values at levels p -+ (K + 32) 2^-23, and the interval likewise in its mass.  Draws whose float32 weight is 0
+ * are ordered after every other draw: they change no value above (if hpd_mass is so close to 1 that rounding leaves no
+ * feasible pair, the interval is the range of the draws with a positive weight).  Widths are compared as exact
+ * float64 differences.  Fixed-order sums, no atomics: a row's outputs are the same bits at any position in the batch
+ * and whether or not quant / corr are requested.
+ * QBOLD_ERR_INVALID for K, C or P out of range, a level or a mass outside (0, 1), quant NULL while P > 0, N < 0, or a
+ * NULL theta, stats or row_out. */
+#define QBOLD_SUMMARY_MIN_K 4
+#define QBOLD_SUMMARY_MAX_K 1024
+#define QBOLD_SUMMARY_MAX_C 8
+#define QBOLD_SUMMARY_MAX_P 8
+int qbold_draw_summary(const qbold_ctx* ctx, const float* log_w, const float* theta, int C, const float* mask, int K,
+                       const float* probs_host, int P, float hpd_mass, float* stats, float* quant, float* row_out,
+                       float* corr, int64_t N, void* stream);
+
 /* Semi-amortised inference (Kim et al. 2018; Cremer et al. 2018): refine each voxel's posterior, starting from given
  * encoder heads, by `steps` gradient steps on that voxel's own objective
  *   E_q[nll(x | y)] + KL(q || prior)   (exact closed-form KL of the logit-space Gaussians, sigma fixed, no TV term)

@@ -19,6 +19,10 @@ QBOLD_PPC_OUT = 6     # columns of qbold_posterior_predictive's out
 QBOLD_PSIS_MIN_K = 25     # qbold_psis: the draws per row a wave holds
 QBOLD_PSIS_MAX_K = 1024
 QBOLD_PSIS_MAX_C = 8
+QBOLD_SUMMARY_MIN_K = 4   # qbold_draw_summary
+QBOLD_SUMMARY_MAX_K = 1024
+QBOLD_SUMMARY_MAX_C = 8
+QBOLD_SUMMARY_MAX_P = 8
 QBOLD_LOO_OUT = 6     # columns of qbold_loo's out
 QBOLD_CAL_OUT = 6     # columns of qbold_calibration's out
 QBOLD_CAL_MAX_L = 1 << 20
@@ -157,6 +161,7 @@ SIGNATURES = {
     "qbold_log_evidence_bwd_anyt": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _P, _P, _P, _I64, _P]),
     "qbold_log_evidence_draws": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _U64, _I64, _P, _P, _I64, _P]),
     "qbold_psis": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _I64, _P]),
+    "qbold_draw_summary": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_float, _P, _P, _P, _P, _I64, _P]),
     "qbold_posterior_grid": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(GridCfg), _P, _P, _P, _P, _I64, _P]),
     "qbold_laplace_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(LaplaceCfg), _P, _P, _I64, _P]),
     "qbold_adapt_posterior": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(AdaptCfg), _U64, _I64, _P, _P, _P, _I64,

@@ -17,7 +17,7 @@ SOURCES = ["ctx.hip", "signal_kernels.hip", "elbo_kernels.hip", "encoder_kernels
            "vi_kernels.hip", "misc_kernels.hip", "elbo_bwd_kernels.hip", "train_kernels.hip", "wide_kernels.hip", "wide_fused_kernels.hip",
            "iw_kernels.hip", "iw_bwd_kernels.hip", "refine_kernels.hip", "grid_kernels.hip", "ppc_kernels.hip",
            "psis_kernels.hip", "loo_kernels.hip", "calibration_kernels.hip", "laplace_kernels.hip", "adapt_kernels.hip",
-           "design_kernels.hip"]
+           "design_kernels.hip", "summary_kernels.hip"]
 HEADERS = ["canon_layout.h", "qbold_dev.h", "qbold_ctx.h", "elbo_core.h", "signal_grad.h", "encoder_core.h", "wide_common.h",
            "vi_fwd_kernels.inc", os.path.join("..", "..", "include", "qbold_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-fno-gpu-rdc",

@@ -306,6 +306,64 @@ class FineTuner:
                        khat_threshold=psis_khat_threshold(K))
         return res
 
+    def credible_intervals(self, data, mask, prior, q=None, no_samples=256, psis=True, probs=(0.025, 0.5, 0.975),
+                           hpd_mass=0.95, seed=1, voxel0=0, psis_chunk=None):
+        """The uncertainty of the importance-corrected posterior per voxel, from the `no_samples` = K draws of
+        log_evidence() for the same seed and voxel0 (Context.log_evidence_draws), weighted by their Pareto-smoothed
+        importance weights (psis=True: Context.psis(want_weights=True), 25 <= K <= 1024) or by the raw ones
+        (psis=False, 4 <= K <= 1024), and summarised by Context.draw_summary.  Shaped like the data's spatial dims, for
+        (OEF, DBV, R2') along the axis of 3:
+          mean, sd      [..., 3] the weighted moments
+          quantiles     [..., 3, P] at `probs`, by the inverse weighted ECDF: each is one of the draws
+          hpd           [..., 3, 2] the shortest interval that holds hpd_mass
+          corr_oef_dbv  the weighted correlation of OEF and DBV
+          ess           1 / sum w~^2 of the weights used
+          khat          (psis) the tail shape k^ of the voxel's raw weights; khat_threshold beside it
+        NaN outside the mask.  q: heads [..., 5] instead of the encoder's (refine() / laplace() / adapt() output).
+        Computed in voxel chunks by log_evidence(psis=True)'s rule (per-draw buffers under 256 MiB, or psis_chunk
+        voxels); chunks pass their own voxel0, so the result does not depend on the chunking."""
+        K = int(no_samples)
+        if psis and not 25 <= K <= 1024:   # QBOLD_PSIS_MIN_K, QBOLD_PSIS_MAX_K
+            raise ValueError("credible_intervals(psis=True) needs 25 <= no_samples <= 1024")
+        if not 4 <= K <= 1024:   # QBOLD_SUMMARY_MIN_K, QBOLD_SUMMARY_MAX_K
+            raise ValueError("credible_intervals needs 4 <= no_samples <= 1024")
+        tr = self._trainer
+        self._check_mvn_family("credible_intervals")
+        T = data.shape[-1]
+        x = _flat(data, T)
+        N = x.shape[0]
+        m = None if mask is None else mask.reshape(-1)
+        p5 = _flat(prior, prior.shape[-1]).contiguous()
+        q, sg = self._heads_and_sigma(data, q)
+        probs = tuple(float(p) for p in probs)
+        P = len(probs)
+        chunk = int(psis_chunk) if psis_chunk else max((256 << 20) // (16 * K) - 1, 1)   # log_w + theta: 16 K bytes
+        if chunk < 1:
+            raise ValueError("psis_chunk must be positive")
+        new = lambda *s: torch.empty((N,) + s, dtype=torch.float32, device=x.device)   # noqa: E731
+        stats, quant, row_out, corr = new(3, 4), new(3, P), new(2), new(3)
+        khat = new() if psis else None
+        for a in range(0, N, chunk):
+            b = min(a + chunk, N)
+            mc = None if m is None else m[a:b]
+            lw, th = tr._ctx.log_evidence_draws(x[a:b], mc, q[a:b], p5[a:b], sg[a:b], K, seed=seed, voxel0=voxel0 + a,
+                                                want_theta=True)
+            if psis:
+                po, _, lw = tr._ctx.psis(lw, None, mc, want_weights=True)
+                khat[a:b] = po[:, 0]
+            st, qt, ro, cr = tr._ctx.draw_summary(th, lw, mc, probs=probs, hpd_mass=hpd_mass, want_corr=True)
+            stats[a:b], row_out[a:b], corr[a:b] = st, ro, cr
+            if P:
+                quant[a:b] = qt
+        lead = data.shape[:-1]
+        res = dict(mean=stats[..., 0].reshape(lead + (3,)), sd=stats[..., 1].reshape(lead + (3,)),
+                   quantiles=quant.reshape(lead + (3, P)), hpd=stats[..., 2:4].reshape(lead + (3, 2)),
+                   corr_oef_dbv=corr[:, 0].reshape(lead), ess=row_out[:, 0].reshape(lead), probs=probs)
+        if psis:
+            from .ops import psis_khat_threshold
+            res.update(khat=khat.reshape(lead), khat_threshold=psis_khat_threshold(K))
+        return res
+
     def _check_mvn_family(self, what):
         if not self._trainer._use_mvg:
             raise NotImplementedError(
@@ -989,7 +1047,8 @@ class EncoderTrainer:
     def save_predictions(self, model, data, filename, transform_directory=None, use_first_op=True,
                          fine_tuner_model=None, priors=None, iw_samples=None, refine_steps=None,
                          posterior_grid=None, ppc_samples=None, refine_smoothness_weight=0.0, psis=False,
-                         loo_samples=None, laplace=False, adapt_rounds=None, identifiability=False):
+                         loo_samples=None, laplace=False, adapt_rounds=None, identifiability=False,
+                         interval_samples=None):
         """model.py:772-887: write `<filename>_{oef,dbv,r2p,logstds}.nii.gz` (posterior means of
         OEF / DBV / R2' over 200 draws and their variances) and, with a fine tuner,
         `_likelihood` (per-voxel NLL averaged over 100 stochastic passes), `_kl` (100-draw KL to
@@ -1035,6 +1094,12 @@ class EncoderTrainer:
         determine at the encoder's posterior means (FineTuner.identifiability) as `_oef_crlb`, `_dbv_crlb`, `_r2p_crlb`
         (data-only Cramer-Rao sds), `_crlbcorr` and `_crlbkappa` (correlation and conditioning of the data information),
         zero outside the mask; these maps join the returned dict.
+        interval_samples = K (with a fine tuner, 25 <= K <= 1024; this package's addition, default None writes nothing
+        new): credible intervals of the importance-corrected posterior from K draws under their Pareto-smoothed weights
+        (FineTuner.credible_intervals; the adapted heads when adapt_rounds is given) as `_oef_is_lo`, `_oef_is_hi`,
+        `_dbv_is_lo`, `_dbv_is_hi`, `_r2p_is_lo`, `_r2p_is_hi` (the 2.5 % and 97.5 % weighted quantiles), `_oef_is_sd`,
+        `_dbv_is_sd`, `_r2p_is_sd` and `_oefdbv_is_corr` (0 where an sd is 0: one effective draw), zero outside the
+        mask; these maps join the returned dict.
         data [subj, X, Y, Z, T+1] with the mask last; each map is stored as [X, Y, Z, subj*C].
         `transform_directory/example.nii.gz`, when present, donates its header (:794-797); the
         FSL `applywarp`/`fslmerge` MNI step (:850-879) is preprocessing outside this package and
@@ -1047,6 +1112,8 @@ class EncoderTrainer:
             raise ValueError("save_predictions(adapt_rounds=R) needs a fine tuner (its sigma and the prior maps)")
         if identifiability and not fine_tuner_model:
             raise ValueError("save_predictions(identifiability=True) needs a fine tuner (its sigma and the prior maps)")
+        if interval_samples and not fine_tuner_model:
+            raise ValueError("save_predictions(interval_samples=K) needs a fine tuner (its sigma and the prior maps)")
         data = torch.as_tensor(data, dtype=torch.float32, device=self._ctx.device)
         T = self._ctx.T
         mask = data[..., -1:]
@@ -1125,6 +1192,24 @@ class EncoderTrainer:
                 save_im_data(v, filename + '_' + k)
         if ad_maps:
             iw_maps = dict(ad_maps, **(iw_maps or {}))
+
+        if fine_tuner_model and interval_samples:
+            ci = fine_tuner_model.credible_intervals(data[..., :-1], mask,
+                                                     torch.as_tensor(priors, device=data.device)[..., :self._nq],
+                                                     q=q_adapt, no_samples=int(interval_samples), psis=True,
+                                                     probs=(0.025, 0.975), seed=self._seed + 67)
+            live = mask[..., 0] > 0
+            zero = torch.zeros_like(ci["ess"])
+            ci_maps = {}
+            for i, name in enumerate(("oef", "dbv", "r2p")):
+                ci_maps[name + "_is_lo"] = ci["quantiles"][..., i, 0]
+                ci_maps[name + "_is_hi"] = ci["quantiles"][..., i, 1]
+                ci_maps[name + "_is_sd"] = ci["sd"][..., i]
+            ci_maps["oefdbv_is_corr"] = torch.nan_to_num(ci["corr_oef_dbv"], nan=0.0)   # undefined where an sd is 0
+            ci_maps = {k: torch.where(live, v, zero)[..., None] for k, v in ci_maps.items()}
+            for k, v in ci_maps.items():
+                save_im_data(v, filename + '_' + k)
+            iw_maps = dict(iw_maps or {}, **ci_maps)
 
         if fine_tuner_model and refine_steps:
             x_ft = data[..., :-1]

@@ -615,6 +615,45 @@ class Context:
                                        _ptr(means), _ptr(weights), N, _stream()), "qbold_psis")
         return out, means, weights
 
+    def draw_summary(self, theta, log_w=None, mask=None, probs=(0.025, 0.5, 0.975), hpd_mass=0.95, want_corr=False):
+        """Summaries of the rows of theta [N, K, C] (4 <= K <= 1024, C <= 8) under the weights log_w [N, K] (raw
+        log-weights or psis' `weights`; None: equal weights, the draws of q itself) (qbold_draw_summary): per column the
+        weighted mean and sd, the quantiles at `probs` (at most 8 levels, each inside (0, 1)) by the inverse weighted
+        ECDF -- always one of the draws, no interpolation -- and the shortest interval that holds `hpd_mass`.  Rows
+        with mask <= 0 are not read and come back NaN.
+        Returns (stats [N, C, 4] = (mean, sd, hpd_lo, hpd_hi), quant [N, C, P] or None (no levels), row_out [N, 2] =
+        (ESS = 1 / sum w~^2, largest w~), corr [N, C (C - 1) / 2] = the weighted correlations in the pair order (0,1),
+        (0,2), ..., (C-2,C-1) (want_corr) or None)."""
+        theta = _f32(theta, "theta")
+        if theta.dim() != 3:
+            raise ValueError("theta must be [N, K, C]")
+        N, K, C = theta.shape
+        if log_w is not None:
+            log_w = _f32(log_w, "log_w")
+            if log_w.dim() != 2 or log_w.shape != theta.shape[:2]:
+                raise ValueError("log_w must be [N, K]")
+        mask = _f32(mask, "mask") if mask is not None else None
+        if mask is not None and mask.numel() != N:
+            raise ValueError("mask must hold N values")
+        probs = [float(p) for p in (probs if probs is not None else ())]
+        P = len(probs)
+        if P > _lib.QBOLD_SUMMARY_MAX_P or not all(0.0 < p < 1.0 for p in probs):
+            raise ValueError("probs: at most 8 levels, each strictly inside (0, 1)")
+        if not 0.0 < float(hpd_mass) < 1.0:
+            raise ValueError("hpd_mass must lie strictly inside (0, 1)")
+        if not (_lib.QBOLD_SUMMARY_MIN_K <= K <= _lib.QBOLD_SUMMARY_MAX_K and 1 <= C <= _lib.QBOLD_SUMMARY_MAX_C):
+            raise ValueError("draw_summary needs 4 <= K <= 1024 draws and 1 <= C <= 8 columns")
+        levels = (_lib.C.c_float * max(P, 1))(*probs)   # read on the host
+        stats = torch.empty((N, C, 4), dtype=torch.float32, device=theta.device)
+        quant = torch.empty((N, C, P), dtype=torch.float32, device=theta.device) if P else None
+        row_out = torch.empty((N, 2), dtype=torch.float32, device=theta.device)
+        corr = torch.empty((N, C * (C - 1) // 2), dtype=torch.float32, device=theta.device) if want_corr else None
+        _lib.check(self.lib.qbold_draw_summary(self.handle, _ptr(log_w), _ptr(theta), int(C), _ptr(mask), int(K),
+                                               _lib.C.cast(levels, _lib.C.c_void_p), P, float(hpd_mass), _ptr(stats),
+                                               _ptr(quant), _ptr(row_out), _ptr(corr), N, _stream()),
+                   "qbold_draw_summary")
+        return stats, quant, row_out, corr
+
     def calibration(self, theta_true, q, mask=None, L=255, log_w=None, z=None, seed=1, voxel0=0):
         """Where a known truth falls in each voxel's posterior (qbold_calibration): theta_true [N, 2] = (OEF, DBV), q
         [N, 5] raw heads of the use_mvg family, L draws per voxel (the draws of log_evidence_draws for the same seed

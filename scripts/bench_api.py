@@ -124,6 +124,9 @@ def main():
                                                   (8 * T + 44 + 16 * K) * f),
             f"psis(K={K},262144)": (lambda: ctx.psis(*ready(K), mq), (16 * K + 32) * f),
             f"log_evidence_draws+psis(K={K},262144)": (lambda: draws_psis(K), (8 * T + 76 + 32 * K) * f),
+            # log_w, theta and mask in; stats (48 B), three quantiles per column (36 B) and row_out (8 B) out
+            # (scripts/bench_summary.py has the torch composition beside it, without a mask: 16 K + 92)
+            f"draw_summary(K={K},262144)": (lambda: ctx.draw_summary(*ready(K)[::-1], mq), (16 * K + 4 + 92) * f),
         }
     # calibration against a known truth at L = 255 draws: the kernel regenerates the draws (28 bytes in, 24 out per voxel,
     # 4 L more with weights), and beside it the path it replaces: the rows of log_evidence_draws (16 L bytes per voxel
